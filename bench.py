@@ -11,6 +11,12 @@ x-slabs with a one-plane halo exchange of `d` and two scalar all-reduces per
 iteration (weak scaling: 256^3 cells per GPU; 8 GPUs = 512^3, BASELINE config 4).
 
 Prints ONE JSON line on rank 0.
+
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times one block of exactly K steps, writes its outputs if
+`--dump-outputs DIR` is given and prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+Everything beyond the headline -- the roofline and per-kernel legs, the parity self-checks against the C oracle, the
+fp64 / config 2-5 / Jacobi side legs, the CPU baseline, the other transport's time at N > 1 and the repeated timed
+blocks of short runs -- runs with `--full` only.
 """
 import argparse
 import json
@@ -27,6 +33,10 @@ HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (/opt/skills/guides/MI35
 
 # global grid per world size: 256^3 cells per GPU, slabs along x (axis 0)
 GRIDS = {1: (256, 256, 256), 2: (512, 256, 256), 4: (512, 512, 256), 8: (512, 512, 512)}
+
+# --dump-outputs: cells written per CG vector when the slab holds more (3 vectors x 2^21 x 8 bytes = 48 MiB in fp64 state)
+DUMP_SAMPLE = 1 << 21
+DUMP_SEED = 20240
 
 
 def parse():
@@ -60,10 +70,35 @@ def parse():
     ap.add_argument("--b2b", action="store_true", help="also time back-to-back applies (cache-warm; not the CG number)")
     ap.add_argument("--cpu-iters", type=int, default=0, help="CG iterations of the CPU baseline sample (0 = auto)")
     ap.add_argument("--repeat", type=int, default=0,
-                    help="timed blocks of exactly --steps iterations each (0 = auto: 9 when --steps < 100, else 1); ms_per_step is "
-                         "their median, min / max are reported beside it")
+                    help="timed blocks of exactly --steps iterations each (0 = auto: 1; with --full 9 when --steps < 100); "
+                         "ms_per_step is their median, min / max are reported beside it")
     ap.add_argument("--no-side-legs", action="store_true", help="headline, roofline and parity only (skip config 2 / 3 / 4 / 5 legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline and per-kernel legs, parity self-checks, fp64 and side legs, "
+                         "CPU baseline, the other transport (N > 1), repeated blocks of short runs.  Off: the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one left to the caller (x, r, d: a fixed seeded sample of "
+                         f"{DUMP_SAMPLE} cells each on larger grids; the residual history) as DIR/<name>.npy")
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, torch, eng, fields, rank, world):
+    """--dump-outputs: the CG vectors the timed loop hands back after its last step (the solution x, the residual r, the
+    direction d; state precision, float32 or float64) and the residual history of the last timed block (float64), as
+    DIR/<name>.npy -- DIR/<name>_rank<k>.npy per rank when N > 1.  A vector of more than DUMP_SAMPLE cells is written as
+    the same DUMP_SAMPLE flat indices on every run (numpy default_rng(DUMP_SEED), sorted): at most 48 MiB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    n = fields["x"].numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+        idx = torch.from_numpy(idx).to(fields["x"].device)
+    for name, t in fields.items():
+        flat = t.reshape(-1)
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), (flat if idx is None else flat[idx]).cpu().numpy())
+    np.save(os.path.join(out_dir, f"history{sfx}.npy"), eng.history())
 
 
 def cpu_baseline(args, gres, scene_seed):
@@ -826,10 +861,12 @@ def main():
         assert st_["delta"] == st_["delta"], "NaN residual"
         return dt_, t_enq_
 
-    # A short run (the driver's --steps 20 is a 2.6 ms region) is repeated: 9 blocks of exactly --steps steps each, the
-    # MEDIAN is the reported time, min / max beside it (`steps` stays what was asked for)
-    n_blocks = args.repeat if args.repeat > 0 else (9 if args.steps < 100 else 1)
+    # With --full a short run (the driver's --steps 20 is a 2.6 ms region) is repeated: 9 blocks of exactly --steps steps
+    # each, the MEDIAN is the reported time, min / max beside it (`steps` stays what was asked for).  A plain run: one block
+    n_blocks = args.repeat if args.repeat > 0 else (9 if args.full and args.steps < 100 else 1)
     blocks = [timed_block(args.warmup) for _ in range(n_blocks)]
+    if args.dump_outputs:              # before anything below iterates the engine again
+        dump_outputs(args.dump_outputs, torch, eng, {"x": x, "r": r, "d": d}, rank, world)
     dts = sorted(b_[0] for b_ in blocks)
     dt = dts[len(dts) // 2]
     t_enq = sorted(b_[1] for b_ in blocks)[len(blocks) // 2]
@@ -839,7 +876,7 @@ def main():
                   "reported": "median" if n_blocks > 1 else "the one block"}
 
     # the other transport on the same problem, outside the timed region (diagnostic only)
-    if world > 1 and transport == "p2p":
+    if args.full and world > 1 and transport == "p2p":
         k_alt = max(10, min(args.steps, 100))
         cg_rccl.begin(0.0)
         cg_rccl.iterate(10)
@@ -866,7 +903,7 @@ def main():
     ts_line = None
     sparse_line = None
     ev_over = 0.0
-    if rank == 0 and not args.timed_loop_only:
+    if rank == 0 and args.full and not args.timed_loop_only:
         Nx, Ny, Nz = lgres
         cells_l = Nx * Ny * Nz
         reps = max(20, min(args.steps, 200))
@@ -1067,7 +1104,7 @@ def main():
 
     if rank == 0:
         cb = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             del eng, cg, cg_rccl, b, x, d, r, q, wx, wy, wz, lphi
             torch.cuda.empty_cache()
             cb = cpu_baseline(args, ggrid, seed)
@@ -1097,6 +1134,8 @@ def main():
                                 "for every entry k, E_k from 80 rounding variants of the C oracle (tests/test_history_envelope.py, "
                                 "tests/golden/envelope_*.npz)"),
         }
+        if not args.full:              # a plain run times the steps and checks nothing beyond them
+            del out["roofline"], out["residual_parity"]
         if sparse_line is not None:
             out["sparse_lists"] = sparse_line
         if parity is not None:

@@ -28,7 +28,7 @@ def test_bench_two_ranks_on_one_gpu(transport, extra):
     env = dict(os.environ, MFS_BENCH_SHARED_GPU="1", MFS_P2P_TIMEOUT_MS="5000", **extra)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--edge", "48",
-           "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--transport", transport]
+           "--steps", "20", "--warmup", "3", "--full", "--no-cpu-baseline", "--transport", transport]
     p = subprocess.run(cmd, env=env, cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
     assert p.returncode == 0, p.stdout[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -3,6 +3,7 @@
 # usage: tools/prof_bench.sh <tag> [bench args...]
 set -e
 TAG=${1:-prof}; shift || true
+set -- --full "$@"          # the whole bench line: roofline, parity and side legs beside the timed loop
 R=${GRAFT_REPO_ROOT:-/root/repo}
 export TMPDIR=/tmp
 cd /tmp
@@ -11,7 +12,7 @@ F=$(find $R/gpurun_out/$TAG -name "*kernel_stats.csv" | head -1)
 python3 - "$F" "$R/gpurun_out/$TAG.log" > $R/gpurun_out/${TAG}_summary.txt <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
-print("# rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline", " ".join(sys.argv[3:]))
+print("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline", " ".join(sys.argv[3:]))
 print("# bench line:", [l for l in open(sys.argv[2]) if l.startswith("{")][-1].strip())
 print(f"{'kernel':60s} {'calls':>6s} {'avg_us':>10s} {'min_us':>10s} {'max_us':>10s} {'total_ms':>10s} {'pct':>6s}")
 for r in rows:
@@ -27,7 +28,7 @@ F=$(find $R/gpurun_out/${TAG}_loop -name "*kernel_stats.csv" | head -1)
 python3 - "$F" "$R/gpurun_out/${TAG}_loop.log" > $R/gpurun_out/${TAG}_loop_summary.txt <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
-print("# rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --timed-loop-only")
+print("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --timed-loop-only")
 print("# bench line:", [l for l in open(sys.argv[2]) if l.startswith("{")][-1].strip()[:700])
 print(f"{'kernel':60s} {'calls':>6s} {'avg_us':>10s} {'min_us':>10s} {'max_us':>10s} {'total_ms':>10s} {'pct':>6s}")
 for r in rows:
