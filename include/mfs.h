@@ -488,6 +488,46 @@ int mfs_pcg2d_poll(mfs_pcg2d* h, mfs_stream stream, int64_t* iters_host, int* do
 int64_t mfs_pcg2d_history(mfs_pcg2d* h, double* out_host, int64_t cap, mfs_stream stream);
 
 /* ------------------------------------------------------------------------- */
+/* Viscosity, 2D -- reference solver/ViscosityCGSolver2D.py                      */
+/* ------------------------------------------------------------------------- */
+/* Quirks of the 2D reference kept as they are: a face sample is solid where sphi <= 0 (3D: < 0); boundary faces
+ * (x == 0, x >= shape[0]-1, y == 0, y >= shape[1]-1 of each component's own array) of b / out are never written;
+ * `vol` is lvol / (cell_vol * 0.125) with cell_vol the cell area (:269).  `sv` is never read (not an argument).  */
+/* replaces initialize_solver -- solver/ViscosityCGSolver2D.py:6-103,222-229 */
+int mfs_visc_rhs2d(const int64_t gres[2], double scale, double mu, const void* vx, const void* vy, int v_dt,
+                   const void* sphi, int sphi_dt, const void* vol, int vol_dt, void* b_x, void* b_y, int b_dt,
+                   mfs_stream stream);
+/* replaces matvecmul -- solver/ViscosityCGSolver2D.py:105-207,231-238 */
+int mfs_visc_apply2d(const int64_t gres[2], double scale, double mu, const void* vx, const void* vy, int v_dt,
+                     void* out_x, void* out_y, int out_dt, const void* sphi, int sphi_dt, const void* vol, int vol_dt,
+                     mfs_stream stream);
+/* replaces apply_viscosity -- solver/ViscosityCGSolver2D.py:209-220,240-244 (in place on vx, vy: faces of cells
+ * 1 <= x <= Nx-1, 1 <= y <= Ny-1 whose sample is > 0)                                                        */
+int mfs_visc_writeback2d(const int64_t gres[2], void* vx, void* vy, int v_dt, const void* out_x, const void* out_y,
+                         int out_dt, const void* sphi, int sphi_dt, mfs_stream stream);
+/* the CG loop solver/ViscosityCGSolver2D.py:266-315.  The five CG vectors are FLAT arrays of mfs_vcg2d_dofs()
+ * elements laid out [ x-faces (Nx+1,Ny) | y-faces (Nx,Ny+1) ].  mfs_vcg2d_solve starts from x as bound (x = v,
+ * not zeroed: r0 = b - A v) and returns MFS_NOT_CONVERGED after max_iter iterations (the reference raises
+ * ValueError there, before apply_viscosity).                                                              */
+typedef struct mfs_vcg2d mfs_vcg2d;
+size_t mfs_vcg2d_workspace_bytes(const int64_t gres[2], int dt);
+int64_t mfs_vcg2d_dofs(const int64_t gres[2]);
+int mfs_vcg2d_create(mfs_vcg2d** out_host, const int64_t gres[2], int dt,
+                     void* workspace, size_t workspace_bytes, mfs_stream stream);
+int mfs_vcg2d_destroy(mfs_vcg2d* h);
+/* once per solve: the sphi tests of every face -> class bits, the doubled-grid `vol` -> four fp64 parity planes */
+int mfs_vcg2d_setup(mfs_vcg2d* h, double scale, double mu, const void* sphi, int sphi_dt,
+                    const void* vol, int vol_dt, mfs_stream stream);
+int mfs_vcg2d_bind(mfs_vcg2d* h, void* b, void* x, void* d, void* r, void* q);
+/* out = A v on flat vectors (the loop's stencil launch; bit-identical to mfs_visc_apply2d, boundary faces untouched) */
+int mfs_vcg2d_apply(mfs_vcg2d* h, const void* v, void* out, mfs_stream stream);
+int mfs_vcg2d_solve(mfs_vcg2d* h, double tol, int64_t max_iter, int64_t check_every,
+                    mfs_stream stream, int64_t* iters_host);
+int mfs_vcg2d_poll(mfs_vcg2d* h, mfs_stream stream, int64_t* iters_host, int* done_host,
+                   double* delta_host, double* alpha_host, double* beta_host);
+int64_t mfs_vcg2d_history(mfs_vcg2d* h, double* out_host, int64_t cap, mfs_stream stream);
+
+/* ------------------------------------------------------------------------- */
 /* Notebook grid kernels that bracket the two solves    */
 /* ------------------------------------------------------------------------- */
 /* replaces `extrapolate(gres, num_iter, vx, vy, vz, mx, my, mz)` -- 3D_viscous_fluid_sim.ipynb code cell 7

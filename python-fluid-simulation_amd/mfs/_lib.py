@@ -193,6 +193,19 @@ SIGNATURES = {
     "mfs_pcg2d_solve": (_i, [_p, _d, _i64, _i64, _p, _pi64]),
     "mfs_pcg2d_poll": (_i, [_p, _p, _pi64, _pint, _pd, _pd, _pd]),
     "mfs_pcg2d_history": (_i64, [_p, _pd, _i64, _p]),
+    "mfs_visc_rhs2d": (_i, [_pi64, _d, _d, _p, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p]),
+    "mfs_visc_apply2d": (_i, [_pi64, _d, _d, _p, _p, _i, _p, _p, _i, _p, _i, _p, _i, _p]),
+    "mfs_visc_writeback2d": (_i, [_pi64, _p, _p, _i, _p, _p, _i, _p, _i, _p]),
+    "mfs_vcg2d_workspace_bytes": (_sz, [_pi64, _i]),
+    "mfs_vcg2d_dofs": (_i64, [_pi64]),
+    "mfs_vcg2d_create": (_i, [C.POINTER(_p), _pi64, _i, _p, _sz, _p]),
+    "mfs_vcg2d_destroy": (_i, [_p]),
+    "mfs_vcg2d_setup": (_i, [_p, _d, _d, _p, _i, _p, _i, _p]),
+    "mfs_vcg2d_bind": (_i, [_p, _p, _p, _p, _p, _p]),
+    "mfs_vcg2d_apply": (_i, [_p, _p, _p, _p]),
+    "mfs_vcg2d_solve": (_i, [_p, _d, _i64, _i64, _p, _pi64]),
+    "mfs_vcg2d_poll": (_i, [_p, _p, _pi64, _pint, _pd, _pd, _pd]),
+    "mfs_vcg2d_history": (_i64, [_p, _pd, _i64, _p]),
 }
 
 _lib = None

@@ -216,6 +216,52 @@ def pressure_scene_2d(gres, seed=1, *, bound_size=(1.0, 1.0), vel_dtype=np.float
 
 
 # ----------------------------------------------------------------------------
+# 2D viscosity scene (reference solver/ViscosityCGSolver2D.py)
+# ----------------------------------------------------------------------------
+def viscosity_scene_2d(gres, seed=4, *, bound_size=(1.0, 1.0), vel_dtype=np.float64, mu=1.0, dt=1.0 / 300.0,
+                       rho=1000.0, noise=0.5):
+    """Walls one cell thick and a disc obstacle (sphi, doubled grid), a rectangular liquid body whose edges cut
+    sub-cells (partial `lvol`), and a shear flow plus noise on EVERY face, solid ones included.  sphi is built in
+    doubled-grid index units times the half cell size: the wall's surface (index 2 from each side) and the disc's
+    points at integer distance r from its integer centre are exactly 0.0 on any grid (the 2D solver treats
+    sphi == 0 as solid)."""
+    Nx, Ny = (int(g) for g in gres)
+    size = tuple(float(s) for s in bound_size)
+    cs = (size[0] / Nx, size[1] / Ny)
+    h = 0.5 * min(cs)
+    I = np.arange(2 * Nx + 1, dtype=np.float64)[:, None]
+    J = np.arange(2 * Ny + 1, dtype=np.float64)[None, :]
+    wall = np.minimum(np.minimum(I, 2 * Nx - I), np.minimum(J, 2 * Ny - J)) - 2.0
+    k = max(1, int(round(0.3 * min(Nx, Ny) / 5.0)))
+    ci, cj, r = float(Nx), float(int(round(0.7 * Ny))), 5.0 * k        # 3-4-5 offsets land on the circle exactly
+    disc = np.sqrt((I - ci) ** 2 + (J - cj) ** 2) - r
+    sphi = np.minimum(wall, disc) * h
+    sv = np.zeros((2 * Nx + 1, 2 * Ny + 1, 2))
+
+    # liquid body [lo, hi]: lvol(node) = overlap with the sub-cell box of edge 0.5 cs centred on the node
+    lo = (0.13 * size[0], 0.07 * size[1])
+    hi = (0.81 * size[0], 0.63 * size[1])
+    X, Y = I * 0.5 * cs[0], J * 0.5 * cs[1]
+
+    def overlap(P, l, hh, half):
+        return np.clip(np.minimum(P + half, hh) - np.maximum(P - half, l), 0.0, 2 * half)
+
+    lvol = overlap(X, lo[0], hi[0], 0.25 * cs[0]) * overlap(Y, lo[1], hi[1], 0.25 * cs[1])
+    cx = (np.arange(Nx) + 0.5) * cs[0]
+    cy = (np.arange(Ny) + 0.5) * cs[1]
+    lphi = np.maximum(np.maximum(lo[0] - cx[:, None], cx[:, None] - hi[0]),
+                      np.maximum(lo[1] - cy[None, :], cy[None, :] - hi[1]))
+
+    rng = np.random.default_rng(seed)
+    fy_x = (np.arange(Ny) + 0.5) * cs[1]
+    fx_y = (np.arange(Nx) + 0.5) * cs[0]
+    vx = 1.0 + np.sin(6.0 * fy_x)[None, :] + noise * rng.standard_normal((Nx + 1, Ny))
+    vy = -0.5 * np.cos(5.0 * fx_y)[:, None] + noise * rng.standard_normal((Nx, Ny + 1))
+    return dict(gres=(Nx, Ny), bound_size=size, cell_size=cs, sphi=sphi, sv=sv, lphi=lphi, lvol=lvol,
+                vx=vx.astype(vel_dtype), vy=vy.astype(vel_dtype), dt=float(dt), mu=float(mu), rho=float(rho))
+
+
+# ----------------------------------------------------------------------------
 # viscosity scene (config 3): buckling-like block of viscous fluid above slabs
 # ----------------------------------------------------------------------------
 def _box_sdf(xp, X, Y, Z, centre, half):

@@ -200,3 +200,95 @@ class VcgEngine:
         block (poll()), never from the history, and stay exact"""
         cap = int(self.lib.mfs_pcg3d_history_capacity())
         return 2 * int(self.poll_raw()["iterations"]) + 1 > cap
+
+
+class Vcg2dEngine:
+    """Python owner of one `mfs_vcg2d` engine handle (include/mfs.h): the 2D viscosity CG over flat
+    [x-faces | y-faces] vectors."""
+
+    def __init__(self, gres, dtype, device=None):
+        self.lib = _lib.load()
+        self.gres = T.as_gres(gres)
+        if len(self.gres) != 2:
+            raise ValueError("Vcg2dEngine is 2D")
+        self.dtype = T.state_dtype(dtype)
+        self.code = _lib.MFS_F32 if self.dtype == torch.float32 else _lib.MFS_F64
+        self.device = torch.device("cuda" if device is None else device)
+        g = _lib.i64x(self.gres)
+        self.dofs = int(self.lib.mfs_vcg2d_dofs(g))
+        self.face_shapes = [T.face_shape(self.gres, a) for a in range(2)]
+        nbytes = int(self.lib.mfs_vcg2d_workspace_bytes(g, self.code))
+        if nbytes <= 0:
+            raise _lib.MfsError("mfs_vcg2d_workspace_bytes returned 0")
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        h = C.c_void_p()
+        with torch.cuda.device(self.workspace.device):
+            _lib.check(self.lib.mfs_vcg2d_create(C.byref(h), g, self.code, T.ptr(self.workspace), nbytes, T.stream()),
+                       "mfs_vcg2d_create")
+        self.h = h
+        self.scalars = self.workspace[: _lib.NSCALARS * 8].view(torch.float64)
+
+    def __del__(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            try:
+                self.lib.mfs_vcg2d_destroy(h)
+            except Exception:
+                pass
+
+    def new_vector(self):
+        """flat [x-faces | y-faces] vector plus its two component views"""
+        flat = torch.zeros(self.dofs, dtype=self.dtype, device=self.workspace.device)
+        views, o = [], 0
+        for shp in self.face_shapes:
+            n = int(np.prod(shp))
+            views.append(flat[o:o + n].view(shp))
+            o += n
+        return flat, views
+
+    def setup(self, scale, mu, sphi, vol):
+        sphi = T.dev(sphi, "sphi", T.doubled_shape(self.gres))
+        vol = T.dev(vol, "vol", T.doubled_shape(self.gres))
+        _lib.check(self.lib.mfs_vcg2d_setup(self.h, float(scale), float(mu), T.ptr(sphi), T.code(sphi), T.ptr(vol),
+                                            T.code(vol), T.stream()), "mfs_vcg2d_setup")
+
+    def _flat(self, t, name):
+        t = T.dev(t, name, (self.dofs,))
+        if t.dtype != self.dtype:
+            raise TypeError(f"{name} must be {self.dtype}")
+        return t
+
+    def apply(self, v, out):
+        """out = A v (faces without an equation untouched); setup() first"""
+        v, out = self._flat(v, "v"), self._flat(out, "out")
+        _lib.check(self.lib.mfs_vcg2d_apply(self.h, T.ptr(v), T.ptr(out), T.stream()), "mfs_vcg2d_apply")
+
+    def bind(self, b, x, d, r, q):
+        ts = [self._flat(a, n) for a, n in ((b, "b"), (x, "x"), (d, "d"), (r, "r"), (q, "q"))]
+        _lib.check(self.lib.mfs_vcg2d_bind(self.h, *[T.ptr(t) for t in ts]), "mfs_vcg2d_bind")
+        self._bound = ts
+
+    def poll(self):
+        it, done = C.c_int64(), C.c_int()
+        delta, alpha, beta = C.c_double(), C.c_double(), C.c_double()
+        _lib.check(self.lib.mfs_vcg2d_poll(self.h, T.stream(), C.byref(it), C.byref(done), C.byref(delta),
+                                           C.byref(alpha), C.byref(beta)), "mfs_vcg2d_poll")
+        return dict(iterations=it.value, done=bool(done.value), delta=delta.value, alpha=alpha.value,
+                    beta=beta.value)
+
+    def solve(self, tol, max_iter, check_every=32):
+        it = C.c_int64()
+        st = _lib.check(self.lib.mfs_vcg2d_solve(self.h, float(tol), int(max_iter), int(check_every), T.stream(),
+                                                 C.byref(it)), "mfs_vcg2d_solve")
+        return st == _lib.MFS_OK, it.value
+
+    def history(self):
+        cap = int(self.lib.mfs_pcg3d_history_capacity())
+        buf = np.empty(cap, dtype=np.float64)
+        n = self.lib.mfs_vcg2d_history(self.h, buf.ctypes.data_as(C.POINTER(C.c_double)), cap, T.stream())
+        _lib.check(int(n), "mfs_vcg2d_history")
+        return buf[: int(n)].copy()
+
+    def history_truncated(self):
+        cap = int(self.lib.mfs_pcg3d_history_capacity())
+        return 2 * int(self.poll()["iterations"]) + 1 > cap
