@@ -284,6 +284,8 @@ class PressureCGSolver3D:
 def pressure_rhs2d(cell_size, gres, vx, vy, sphi, sv, lphi, b, wx, wy):
     """solver/PressureCGSolver2D.py:6-44."""
     Nx, Ny = (int(g) for g in gres)
+    if Nx < 3 or Ny < 3:
+        return                              # no interior cell: the reference's kernel writes nothing
     cs = [float(c) for c in cell_size]
     sv = np.asarray(sv, F64)
 
@@ -309,6 +311,8 @@ def pressure_rhs2d(cell_size, gres, vx, vy, sphi, sv, lphi, b, wx, wy):
 def pressure_apply2d(gres, v, out, wx, wy, lphi):
     """solver/PressureCGSolver2D.py:46-100."""
     Nx, Ny = (int(g) for g in gres)
+    if Nx < 3 or Ny < 3:
+        return                              # no interior cell: nothing written
 
     def sh(a, dx, dy):
         return np.asarray(a, F64)[1 + dx:Nx - 1 + dx, 1 + dy:Ny - 1 + dy]

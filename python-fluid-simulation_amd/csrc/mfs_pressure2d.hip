@@ -58,7 +58,11 @@ k_pressure_apply2d(Grid2 g, const void* v, void* out, int dt, const void* wx, co
   double acc = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const int y = (int)(i % g.Ny), x = (int)(i / g.Ny);
-    if (x == 0 || x >= g.Nx - 1 || y == 0 || y >= g.Ny - 1) continue;
+    if (x == 0 || x >= g.Nx - 1 || y == 0 || y >= g.Ny - 1) {
+      // never written, yet the reference's d.q sums the whole arrays: a shared buffer's stale q counts here
+      if (partial) acc += ldx(v, dt, i) * ldx(out, dt, i);
+      continue;
+    }
     const double phi = ldx(lphi, ldt, i);
     if (!(phi < 0)) { stx(out, dt, i, 0.0); continue; }
     double val = 0.0, diag = 0.0;

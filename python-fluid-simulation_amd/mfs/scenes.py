@@ -215,6 +215,52 @@ def pressure_scene_2d(gres, seed=1, *, bound_size=(1.0, 1.0), vel_dtype=np.float
                 vx=vx, vy=vy)
 
 
+def pressure_scene_2d_edges(gres, seed=3, *, vel_dtype=np.float64):
+    """The level-set edges of the 2D pressure solver on exact binary-fraction geometry (cell size 1, integer offsets).
+
+    sphi (doubled grid, value = distance in cells): walls whose surface passes through the corner nodes at x = 1,
+    x = Nx - 1, y = 1, y = Ny - 1 (exact 0.0) and a diamond obstacle at an integer centre (half-integer values at the
+    corner nodes: its edges are cut in half, w = 0.5).
+    Every second exact zero is stored as -0.0; both are "not solid" (`< 0` is false).
+    lphi (cell centres): a liquid pool along the longer axis u, cell rows v < L(u) liquid (integer depths), the
+    surface row v = L(u) patterned by u mod 4:
+      0: 0.0 (air at exactly zero)           1: -1e-4 just below, +1.0 at the surface (theta clamp in apply and update)
+      2: -0.0 (air at a signed zero)         3: -1e-4 just below, 0.0 at the surface (theta exactly 1)
+    L alternates between two depths every 4 columns, so thin grids (one interior row or column) meet every pattern
+    both as a liquid and as an air interior cell.  Solid velocity is on."""
+    Nx, Ny = (int(g) for g in gres)
+    I = np.arange(2 * Nx + 1, dtype=np.float64)[:, None] * 0.5
+    J = np.arange(2 * Ny + 1, dtype=np.float64)[None, :] * 0.5
+    wall = np.minimum(np.minimum(I, Nx - I), np.minimum(J, Ny - J)) - 1.0
+    diamond = np.abs(I - (Nx // 2)) + np.abs(J - (Ny // 2)) - max(1, min(Nx, Ny) // 4) - 0.5
+    sphi = np.minimum(wall, diamond)
+    ii, jj = np.meshgrid(np.arange(2 * Nx + 1), np.arange(2 * Ny + 1), indexing="ij")
+    sphi[(sphi == 0) & ((ii + jj) // 2 % 2 == 1)] = -0.0
+    sv = np.stack([0.3 * np.sin(0.37 * J) + 0 * I, -0.2 * np.cos(0.23 * I) + 0 * J], axis=-1)
+
+    transpose = Ny > Nx                       # u: the longer axis, v: the other
+    Nu, Nv = (Ny, Nx) if transpose else (Nx, Ny)
+    u = np.arange(Nu)
+    L = np.clip(Nv // 2 + (u // 4) % 2, 1, max(1, Nv - 1))
+    f = np.arange(Nv, dtype=np.float64)[None, :] - L[:, None]          # (Nu, Nv): negative below the surface
+    for k in range(Nu):
+        s, pat = int(L[k]), k % 4
+        if pat == 0:
+            f[k, s] = 0.0
+        elif pat == 1:
+            f[k, s - 1], f[k, s] = -1e-4, 1.0
+        elif pat == 2:
+            f[k, s] = -0.0
+        else:
+            f[k, s - 1], f[k, s] = -1e-4, 0.0
+    lphi = np.ascontiguousarray(f.T if transpose else f)
+    rng = np.random.default_rng(seed)
+    vx = rng.standard_normal((Nx + 1, Ny)).astype(vel_dtype)
+    vy = rng.standard_normal((Nx, Ny + 1)).astype(vel_dtype)
+    return dict(gres=(Nx, Ny), bound_size=(float(Nx), float(Ny)), cell_size=(1.0, 1.0), sphi=sphi, sv=sv,
+                lphi=lphi, vx=vx, vy=vy)
+
+
 # ----------------------------------------------------------------------------
 # 2D viscosity scene (reference solver/ViscosityCGSolver2D.py)
 # ----------------------------------------------------------------------------

@@ -125,8 +125,14 @@ def gen_pressure3d(name, gres, seed, vel_dtype, solid_velocity, tol=1e-3, all_fl
         alpha=slv.alpha, beta=slv.beta, delta=slv.delta)
 
 
-def gen_pressure2d(name, gres, seed, solid_velocity, tol=1e-6):
-    sc = scenes.pressure_scene_2d(gres, seed, solid_velocity=solid_velocity)
+def _scene2d(gres, seed, solid_velocity, edges):
+    if edges:
+        return scenes.pressure_scene_2d_edges(gres, seed)
+    return scenes.pressure_scene_2d(gres, seed, solid_velocity=solid_velocity)
+
+
+def gen_pressure2d(name, gres, seed, solid_velocity, tol=1e-6, edges=False):
+    sc = _scene2d(gres, seed, solid_velocity, edges)
     g = C(gres, np.int64)
     bsz = C(sc["bound_size"], np.float64)
     sphi, sv, lphi = C(sc["sphi"]), C(sc["sv"]), C(sc["lphi"])
@@ -155,11 +161,59 @@ def gen_pressure2d(name, gres, seed, solid_velocity, tol=1e-6):
     np.savez_compressed(
         os.path.join(HERE, name + ".npz"),
         kind="pressure2d", gres=np.array(gres), bound_size=np.array(sc["bound_size"]), tol=tol,
-        seed=seed, solid_velocity=solid_velocity,
+        seed=seed, solid_velocity=solid_velocity or edges, edges=edges,
         in_vx=sc["vx"], in_vy=sc["vy"], sphi=sc["sphi"], sv=sc["sv"], lphi=sc["lphi"],
         wx=np.asarray(wx), wy=np.asarray(wy), b=np.asarray(b), q1=np.asarray(q1),
         history=hist, iters=iters, x=np.asarray(slv.x),
         out_vx=np.asarray(vx), out_vy=np.asarray(vy))
+    assert hist[-1] < tol ** 2, f"{name} did not converge at tol={tol}"
+
+
+def stale_ring(gres, base):
+    """a deterministic, non-zero pattern on the boundary ring of a cell array (zero inside)"""
+    Nx, Ny = gres
+    a = np.zeros(gres)
+    ring = np.ones(gres, dtype=bool)
+    ring[1:Nx - 1, 1:Ny - 1] = False
+    k = np.arange(Nx * Ny, dtype=np.float64).reshape(gres)
+    a[ring] = base * (1.0 + 0.125 * (k[ring] % 7) - 0.25 * (k[ring] % 3))
+    return a
+
+
+def gen_pressure2d_stale(name, gres, seed, solid_velocity, max_iter, edges=False):
+    """The class solve with the shared CGSolverBuffer's boundary ring pre-filled (b, q, d, r): the reference never
+    writes those cells, yet its CG loop runs over the whole arrays.  tol = 0 and a fixed max_iter (no convergence)."""
+    sc = _scene2d(gres, seed, solid_velocity, edges)
+    g = C(gres, np.int64)
+    bsz = C(sc["bound_size"], np.float64)
+    sphi, sv, lphi = C(sc["sphi"]), C(sc["sv"]), C(sc["lphi"])
+    pre = {k: stale_ring(gres, v) for k, v in (("b", 0.5), ("q", -0.25), ("d", 3.0), ("r", -2.0))}
+    buf = RB.CGSolverBuffer(g)
+    for k, a in pre.items():
+        getattr(buf, k)[...] = C(a)
+    slv = RP2.PressureCGSolver2D(buf, g, bsz)
+    slv.max_iter = max_iter
+    vx, vy = C(sc["vx"]), C(sc["vy"])
+    logger = _SumLogger(cp)
+    RP2.cp = logger
+    try:
+        slv.solve(vx, vy, sphi, sv, lphi, tol=0.0)
+    finally:
+        RP2.cp = cp
+    hist = np.array(logger.log)
+    iters = (len(hist) - 1) // 2
+    assert iters == max_iter
+    print(f"  {name}: gres={gres} iters={iters} delta0={hist[0]:.4e} delta_end={hist[-1]:.4e}")
+    np.savez_compressed(
+        os.path.join(HERE, name + ".npz"),
+        kind="pressure2d_stale", gres=np.array(gres), bound_size=np.array(sc["bound_size"]), tol=0.0,
+        max_iter=max_iter, seed=seed, solid_velocity=solid_velocity, edges=edges,
+        in_vx=sc["vx"], in_vy=sc["vy"], sphi=sc["sphi"], sv=sc["sv"], lphi=sc["lphi"],
+        pre_b=pre["b"], pre_q=pre["q"], pre_d=pre["d"], pre_r=pre["r"],
+        wx=np.asarray(slv.wx), wy=np.asarray(slv.wy),
+        history=hist, iters=iters, x=np.asarray(slv.x), b=np.asarray(buf.b), d=np.asarray(buf.d),
+        r=np.asarray(buf.r), q=np.asarray(buf.q), out_vx=np.asarray(vx), out_vy=np.asarray(vy),
+        alpha=slv.alpha, beta=slv.beta, delta=slv.delta)
 
 
 def gen_viscosity3d(name, gres, seed, vel_dtype, tol=1e-3, mu=None):
@@ -283,6 +337,13 @@ CASES = [
     ("p3d_e_allfluid_12", lambda n: gen_pressure3d(n, (12, 12, 12), 8, np.float64, False, all_fluid=True)),
     ("p2d_a_64", lambda n: gen_pressure2d(n, (64, 64), 1, False)),
     ("p2d_b_24x20_sv", lambda n: gen_pressure2d(n, (24, 20), 2, True)),
+    # level-set edges (exact and signed zeros, theta clamp hits), odd / thin grids: mfs.scenes.pressure_scene_2d_edges
+    ("p2d_c_33x17_edges", lambda n: gen_pressure2d(n, (33, 17), 3, True, edges=True)),
+    # one interior column / row: own prefix, their GPU history window is measured (test_pressure2d_oracle_gpu.py)
+    ("p2dt_d_3x130", lambda n: gen_pressure2d(n, (3, 130), 4, True, edges=True)),
+    ("p2dt_e_130x3", lambda n: gen_pressure2d(n, (130, 3), 5, True, edges=True)),
+    # stale boundary ring in the shared buffer (a prefix the p2d_ tests do not glob)
+    ("p2dq_stale_24x20", lambda n: gen_pressure2d_stale(n, (24, 20), 2, True, max_iter=10)),
     ("v3d_a_12", lambda n: gen_viscosity3d(n, (12, 12, 12), 3, np.float32)),
     ("v3d_b_10x12x14", lambda n: gen_viscosity3d(n, (10, 12, 14), 4, np.float64)),
     ("v3d_c_16_mu50", lambda n: gen_viscosity3d(n, (16, 16, 16), 5, np.float32, mu=50.0)),
