@@ -677,8 +677,23 @@ def _corner_weights(w, ix, iy, iz):
     return cw(ix, w[:, 0]) * cw(iy, w[:, 1]) * cw(iz, w[:, 2])
 
 
-def density_splat3d(bound_min, cell_size, gres, px, pm, pvol, gm, gvol):
-    """initialize_density_kernel :8-36 (order of the atomic adds is unspecified in the reference)."""
+def _scatter_stats(stats, shape, idx, **terms):
+    """Per target node of a scatter: stats["K"] += the number of contributions (zero-valued ones included, so K is what
+    scattering ones gives) and stats["S_<name>"] += the sum of their absolute values in float64.  With these a sum of
+    the same terms in any order, every add rounded at unit roundoff u, lies within (K - 1) u S of the exact one."""
+    if stats is None:
+        return
+    n = int(np.prod(shape))
+    flat = np.ravel_multi_index(idx, shape)
+    stats["K"] = stats.get("K", 0) + np.bincount(flat, minlength=n).reshape(shape)
+    for name, t in terms.items():
+        key = "S_" + name
+        stats[key] = stats.get(key, 0.0) + np.bincount(flat, weights=np.abs(np.asarray(t, F64)), minlength=n).reshape(shape)
+
+
+def density_splat3d(bound_min, cell_size, gres, px, pm, pvol, gm, gvol, stats=None):
+    """initialize_density_kernel :8-36 (order of the atomic adds is unspecified in the reference).  The sums are formed
+    in the dtype of `gm` / `gvol`; `stats` (a dict) receives K, S_m, S_vol per cell (see _scatter_stats)."""
     Nx, Ny, Nz = (int(g) for g in gres)
     gi, w = _particle_cell(px, bound_min, cell_size, (0.5, 0.5, 0.5))
     m = np.asarray(pm, F64)
@@ -691,6 +706,7 @@ def density_splat3d(bound_min, cell_size, gres, px, pm, pvol, gm, gvol):
                 weight = _corner_weights(w, ix, iy, iz)
                 np.add.at(gm, (cx, cy, cz), weight * m)
                 np.add.at(gvol, (cx, cy, cz), weight * float(pvol))
+                _scatter_stats(stats, gm.shape, (cx, cy, cz), m=weight * m, vol=weight * float(pvol))
 
 
 def _nonsolid_frac(gres, wx, wy, wz):
@@ -844,8 +860,10 @@ def _nb_particle_cell(px, bound_min, cell_size, bias, centre_offset=None):
     return x32, gi, gx32
 
 
-def nb_p2g_scatter(px, pm, pv, pca, gm, gv, bound_min, gres, grid_bias, cell_size, axis):
-    """p2g_particle (code cell 2): APIC scatter of mass and momentum of component `axis` to its faces."""
+def nb_p2g_scatter(px, pm, pv, pca, gm, gv, bound_min, gres, grid_bias, cell_size, axis, stats=None):
+    """p2g_particle (code cell 2): APIC scatter of mass and momentum of component `axis` to its faces.  The sums are
+    formed in the dtype of `gm` / `gv` (float64 arrays give the float64 reference); `stats` (a dict) receives K, S_m, S_v
+    per face (see _scatter_stats)."""
     Nx, Ny, Nz = (int(g) for g in gres)
     cs = np.asarray(cell_size, F64)
     x32, gi, gx32 = _nb_particle_cell(px, bound_min, cs, grid_bias)
@@ -866,8 +884,10 @@ def nb_p2g_scatter(px, pm, pv, pca, gm, gv, bound_min, gres, grid_bias, cell_siz
                 cv = ((d64[:, 0] + ix * cs[0]) * pca[:, 0] + (d64[:, 1] + iy * cs[1]) * pca[:, 1]
                       + (d64[:, 2] + iz * cs[2]) * pca[:, 2])
                 weight = wx * wy * wz
-                np.add.at(gm, (cx, cy, cz), (weight * m).astype(gm.dtype))
-                np.add.at(gv, (cx, cy, cz), (weight * m * (v32[:, axis].astype(F64) + cv)).astype(gv.dtype))
+                tm, tv = weight * m, weight * m * (v32[:, axis].astype(F64) + cv)
+                np.add.at(gm, (cx, cy, cz), tm.astype(gm.dtype))
+                np.add.at(gv, (cx, cy, cz), tv.astype(gv.dtype))
+                _scatter_stats(stats, gm.shape, (cx, cy, cz), m=tm, v=tv)
 
 
 def nb_p2g_normalize(gm, gv):
@@ -876,14 +896,18 @@ def nb_p2g_normalize(gm, gv):
     gv[m] = gv[m] / gm[m]
 
 
-def nb_g2p_gather(bound_min, gres, grid_bias, cell_size, axis, px, pv, pca, gv):
-    """g2p_particle (code cell 3): trilinear velocity and its affine row, in the kernel's accumulation order."""
+def nb_g2p_gather(bound_min, gres, grid_bias, cell_size, axis, px, pv, pca, gv, stats=None):
+    """g2p_particle (code cell 3): trilinear velocity and its affine row, in the kernel's accumulation order and in the
+    dtype of `pv` / `pca` -- the reference adds into the array element (`pv[P, axis] += ...`), so with float32 particle
+    arrays each of the 8 partial sums is rounded to float32.  `stats` (a dict) receives per particle the sums of the
+    absolute terms: S_v (P,) and S_c (P, 3)."""
     Nx, Ny, Nz = (int(g) for g in gres)
     cs = np.asarray(cell_size, F64)
     x32, gi, gx32 = _nb_particle_cell(px, bound_min, cs, grid_bias)
     w = (np.abs(gx32 - x32).astype(F64) / cs).astype(F32).astype(F64)
     pca[:, :] = 0
-    vel = np.zeros(len(x32))
+    vel = np.zeros(len(x32), dtype=pv.dtype)
+    s_v, s_c = np.zeros(len(x32)), np.zeros((len(x32), 3))
     G = np.asarray(gv)
     for ix in (0, 1):
         for iy in (0, 1):
@@ -895,11 +919,17 @@ def nb_g2p_gather(bound_min, gres, grid_bias, cell_size, axis, px, pv, pca, gv):
                 wy = 1 - iy + (2 * iy - 1) * w[:, 1]
                 wz = 1 - iz + (2 * iz - 1) * w[:, 2]
                 g = G[cx, cy, cz].astype(F64)
-                vel = vel + wx * wy * wz * g
-                pca[:, 0] += (2 * ix - 1) * wy * wz * g / cs[0]
-                pca[:, 1] += wx * (2 * iy - 1) * wz * g / cs[1]
-                pca[:, 2] += wx * wy * (2 * iz - 1) * g / cs[2]
+                terms = (wx * wy * wz * g, (2 * ix - 1) * wy * wz * g / cs[0], wx * (2 * iy - 1) * wz * g / cs[1],
+                         wx * wy * (2 * iz - 1) * g / cs[2])
+                vel = (vel + terms[0]).astype(pv.dtype)
+                pca[:, 0] += terms[1]
+                pca[:, 1] += terms[2]
+                pca[:, 2] += terms[3]
+                s_v += np.abs(terms[0])
+                s_c += np.abs(np.stack(terms[1:], axis=1))
     pv[:, axis] = vel
+    if stats is not None:
+        stats["S_v"], stats["S_c"] = s_v, s_c
 
 
 def nb_fluid_levelset(px, phi, bound_min, cell_size, gdx, gres):
@@ -923,9 +953,10 @@ def nb_fluid_levelset(px, phi, bound_min, cell_size, gdx, gres):
                 np.minimum.at(phi, (ii[:, 0], ii[:, 1], ii[:, 2]), n ** 0.5 - r)
 
 
-def nb_fluid_volume(bound_min, cell_size, gres, px, pvol, gvol):
+def nb_fluid_volume(bound_min, cell_size, gres, px, pvol, gvol, stats=None):
     """compute_fluid_volume (code cell 6): trilinear splat of the particle volume onto the doubled-grid nodes,
-    clamped to the node's cell volume."""
+    clamped to the node's cell volume.  `stats` (a dict) receives K and S_vol of the splat per node, before the clamp
+    (see _scatter_stats)."""
     Nx, Ny, Nz = (int(g) for g in gres)
     cs = np.asarray(cell_size, F64)
     gvol[...] = 0.0
@@ -940,6 +971,7 @@ def nb_fluid_volume(bound_min, cell_size, gres, px, pvol, gvol):
                 weight = ((ix + ((-1) ** ix) * (1 - w[:, 0])) * (iy + ((-1) ** iy) * (1 - w[:, 1]))
                           * (iz + ((-1) ** iz) * (1 - w[:, 2])))
                 np.add.at(gvol, (cx, cy, cz), weight * float(pvol))
+                _scatter_stats(stats, gvol.shape, (cx, cy, cz), vol=weight * float(pvol))
     np.minimum(gvol, float(np.prod(cs)), out=gvol)
 
 

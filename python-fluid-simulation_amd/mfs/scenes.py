@@ -453,3 +453,68 @@ def particle_scene_3d(gres, seed=0, *, per_cell=3, bound_min=(-0.3, 0.0, -0.3)):
     aff = [2.0 * rng.standard_normal((n, 3)) for _ in range(3)]
     return dict(gres=(Nx, Ny, Nz), bound_min=tuple(float(b) for b in bound_min), bound_size=tuple(float(v) for v in size),
                 gdx=gdx, px=px, pm=pm, pv=pv, pcx=aff[0], pcy=aff[1], pcz=aff[2], pvol=float(pvol))
+
+
+def particle_stress_scene_3d(gres=(100, 44, 67), seed=0, *, bulk=300000, per_wall=5000, bound_min=(-0.3, 0.0, -0.3),
+                             bound_size=(1.2, 0.5, 0.9)):
+    """A particle set built to reach what `particle_scene_3d` and a mesh-ordered block never do in the particle <-> grid
+    transfers and their tile-sorted forms (tiles of 8^3 cells, csrc/mfs_particles.hip); tests/test_particle_stress_scene.py
+    asserts each item:
+      * extents that are no multiple of 8 and all different (partial tiles on every axis), three different cell sizes,
+        float32 `bound_min` / `bound_size` and float64 cell sizes like the notebook's containers;
+      * more particles than the tile-sort threshold, in SHUFFLED order: 256 consecutive particles lie in far more than
+        the 128 tiles a workgroup's table of the sort holds;
+      * at each of the six walls particles within 1.5 cells inside to 2 cells outside (low clamp of the base index, high
+        clamp of the +1 / +2 neighbours), particles exactly at `bound_min`, exactly on the far walls and on interior
+        cell faces (a zero weight on four of the eight corners);
+      * the bulk fills y below 30 cells only: the tile layer of cells 32..39 stays empty but for ONE particle, every
+        bulk tile holds several hundred (more than one pass of a 256-thread tile loop);
+      * masses and velocities of both signs over three decades.
+    numpy only; the same arrays for the same arguments."""
+    N = np.array([int(g) for g in gres], np.int64)
+    if N[1] < 42 or N[0] < 16 or N[2] < 16:
+        raise ValueError("particle_stress_scene_3d needs gres[1] >= 42 (an empty tile layer above the bulk) and 16 cells elsewhere")
+    bmin = np.asarray(bound_min, np.float32)
+    bsz = np.asarray(bound_size, np.float32)
+    cs = bsz / N                                            # float64, as float32 / int64 is in the notebook
+    rng = np.random.default_rng(seed + 3000)
+    b64 = bmin.astype(np.float64)
+    ytop = 30.0                                             # the bulk's ceiling, in cells
+    hi = np.array([N[0], ytop, N[2]], np.float64)
+    parts = [rng.uniform([0.0, 0.0, 0.0], hi, size=(bulk, 3))]                 # in cells
+    for a in range(3):
+        for side in (0, 1):
+            q = rng.uniform([0.0, 0.0, 0.0], hi if a != 1 else N.astype(np.float64), size=(per_wall, 3))
+            d = rng.uniform(-2.0, 1.5, size=per_wall)       # distance into the box, cells; negative: outside
+            q[:, a] = d if side == 0 else N[a] - d
+            parts.append(q)
+    X = np.concatenate(parts) * cs + b64
+    # exact positions, float32-representable so that float32 particle arrays keep them: the corner at bound_min, one
+    # coordinate at bound_min, the far walls and the faces N/2, N/4 where those are integers (k * cell_size is a float32
+    # there: bound_size / 2, / 4), the others random in the bulk
+    exact = [bmin.astype(np.float64)]
+    for a in range(3):
+        for k in (0, N[a], N[a] // 2 if N[a] % 2 == 0 else None, N[a] // 4 if N[a] % 4 == 0 else None):
+            if k is None:
+                continue
+            for _ in range(16):
+                q = (rng.uniform([0.0, 0.0, 0.0], hi, size=3) * cs + b64).astype(np.float32)
+                face = np.float32(np.float32(bsz[a] * np.float32(k / N[a])) + bmin[a])
+                # keep the candidate only if the kernels' own arithmetic lands on the integer
+                if (np.float32(face - bmin[a]).astype(np.float64) / cs[a]) == float(k):
+                    q[a] = face
+                    exact.append(q.astype(np.float64))
+    # the lonely particle: centre of a cell in the middle of the empty tile layer
+    lone = (np.array([N[0] // 2 // 8 * 8 + 3.5, 35.5, N[2] // 2 // 8 * 8 + 3.5]) * cs + b64)
+    X = np.concatenate([X, np.asarray(exact), lone[None]])
+    n = len(X)
+    order = rng.permutation(n)
+    X = X[order]
+    pvol = float(np.prod(cs)) / 8
+    sgn = lambda size: np.where(rng.random(size) < 0.3, -1.0, 1.0)  # noqa: E731
+    pm = 1000.0 * pvol * sgn(n) * 10.0 ** rng.uniform(-3.0, 0.0, n)
+    pv = sgn((n, 3)) * 10.0 ** rng.uniform(-2.0, 1.0, (n, 3))
+    aff = [2.0 * rng.standard_normal((n, 3)) for _ in range(3)]
+    return dict(gres=tuple(int(v) for v in N), bound_min=bmin, bound_size=bsz, cell_size=cs, gdx=float(cs.min()),
+                px=X, pm=pm, pv=pv, pcx=aff[0], pcy=aff[1], pcz=aff[2], pvol=pvol,
+                lone=int(np.nonzero(order == n - 1)[0][0]))

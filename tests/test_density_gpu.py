@@ -18,13 +18,29 @@ T = lambda a, dt=None: torch.as_tensor(np.ascontiguousarray(a), device=DEV) if d
 N = lambda t: t.detach().cpu().numpy()  # noqa: E731
 
 
-@pytest.mark.parametrize("name", golden_names("d3d_"))
-def test_module_functions(name):
+def _both_splats(names):
+    """every golden twice: as it runs by default at this size (per-particle atomics) and with the tile-sorted splat
+    (mfs_density_splat3d_tiled, the default from 262 144 particles) forced -- same assertions, same tolerances"""
+    return [pytest.param(n, None, id=n) for n in names] + [pytest.param(n, 1, id=n + "-tiled") for n in names]
+
+
+def _force_splat(tile_min, monkeypatch):
+    import notebook_kernels as NK
+    NK._TILE_ORDERS.clear()
+    if tile_min is not None:
+        monkeypatch.setattr(NK, "TILE_MIN_PARTICLES", tile_min)
+    return NK
+
+
+@pytest.mark.parametrize("name,tile_min", _both_splats(golden_names("d3d_")))
+def test_module_functions(name, tile_min, monkeypatch):
     g = golden(name)
+    NK = _force_splat(tile_min, monkeypatch)
     gres = tuple(int(v) for v in g["gres"])
     cs = np.asarray(g["bound_size"], np.float64) / np.asarray(gres, np.float64)
     gm, gvol = torch.zeros(gres, dtype=torch.float64, device=DEV), torch.zeros(gres, dtype=torch.float64, device=DEV)
     D.initialize_density(g["bound_min"], cs, gres, T(g["px"]), T(g["pm"]), float(g["pvol"]), gm, gvol)
+    assert len(NK._TILE_ORDERS) == (0 if tile_min is None else 1)
     np.testing.assert_allclose(N(gm), g["gm"], rtol=0, atol=1e-11 * np.abs(g["gm"]).max())
     np.testing.assert_allclose(N(gvol), g["gvol_raw"], rtol=0, atol=1e-11 * np.abs(g["gvol_raw"]).max())
     wx, wy, wz, lphi, sphi = T(g["wx"]), T(g["wy"]), T(g["wz"]), T(g["lphi"]), T(g["sphi"])
@@ -80,15 +96,17 @@ def test_engine_operator_matches_stateless_kernel(name, dt):
     assert torch.equal(outs[0], outs[1])          # compressed == dense coefficient access, bit for bit
 
 
-@pytest.mark.parametrize("name", golden_names("d3d_"))
-def test_class_solve_matches_reference(name):
+@pytest.mark.parametrize("name,tile_min", _both_splats(golden_names("d3d_")))
+def test_class_solve_matches_reference(name, tile_min, monkeypatch):
     g = golden(name)
+    NK = _force_splat(tile_min, monkeypatch)
     gres = tuple(int(v) for v in g["gres"])
     buf = CGSolverBuffer(gres, precision="fp64", device=DEV)
     s = D.DensityCGSolver3D(buf, gres, g["bound_min"], g["bound_size"])
     px = T(g["px"])
     s.solve(float(g["rho0"]), float(g["dt"]), px, T(g["pm"]), float(g["pvol"]), None, None, None, T(g["sphi"]), T(g["sv"]),
             T(g["lphi"]), T(g["lvol"]), tol=float(g["tol"]))
+    assert len(NK._TILE_ORDERS) == (0 if tile_min is None else 1)
     h = s.history
     n = min(21, len(h), len(g["history"]))
     np.testing.assert_allclose(h[:n], g["history"][:n], rtol=1e-9)
