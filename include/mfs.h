@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MFS_ABI_VERSION 3   /* = the round the entry-point set last grew in */
+#define MFS_ABI_VERSION 3   /* bumped when an existing entry point changes or goes; additions (the 2D solvers) keep it */
 
 typedef enum { MFS_F32 = 0, MFS_F64 = 1 } mfs_dtype;
 
@@ -457,6 +457,44 @@ int mfs_density_advect3d(void* px, int px_dt, int64_t num_particles, const void*
                          const double grid_bias[3], int axis, mfs_stream stream);
 
 /* ------------------------------------------------------------------------- */
+/* Density solver, 2D -- reference solver/DensityCGSolver2D.py                   */
+/* ------------------------------------------------------------------------- */
+/* The CG loop of DensityCGSolver2D.solve (:274-290) runs on the 2D pressure engine: mfs_pcg2d_setup_density (below,
+ * beside mfs_pcg2d_setup), then bind / solve as for pressure.  Where the 2D kernels differ from their 3D twins it is
+ * the reference that differs: the splat writes gm only, fix_volume reads lvol, the operator has no asymmetric tap. */
+/* replaces initialize_density -- :8-33,197-202: scatters particle mass pm[p] to the 4 surrounding cell centres
+ * (indices clamped to the grid) with fp atomics; px is (P,2) row-major.  ONLY gm is written: the reference's volume
+ * scatter is commented out (:33); pvol and gvol are accepted and unused                                          */
+int mfs_density_splat2d(const int64_t gres[2], const double bound_min[2], const double cell_size[2],
+                        const void* px, int px_dt, const void* pm, int pm_dt, double pvol, int64_t num_particles,
+                        void* gm, void* gvol, int g_dt, mfs_stream stream);
+/* replaces fix_volume -- :35-57,204-211: gvol = min(lvol summed over the cell's nine doubled-grid samples with
+ * weights 1, 1/2, 1/4 -- or the cell volume for an internal fluid cell away from solids --, cell volume * open
+ * fraction); interior cells only, boundary cells of gvol keep what they held                                    */
+int mfs_density_fix_volume2d(const int64_t gres[2], const double cell_size[2], const void* lvol, int lvol_dt,
+                             void* gvol, int g_dt, const void* sphi, int sphi_dt, const void* lphi, int lphi_dt,
+                             const void* wx, const void* wy, int w_dt, mfs_stream stream);
+/* replaces initialize_solver -- :59-83,213-219 */
+int mfs_density_rhs2d(const int64_t gres[2], double rho0, double dt, const double cell_size[2],
+                      const void* gm, const void* gvol, int g_dt, const void* lphi, int lphi_dt,
+                      const void* wx, const void* wy, int w_dt, void* b, int b_dt, mfs_stream stream);
+/* replaces matvecmul -- :85-139,221-225 (stateless; boundary cells of `out` are not written): the pressure 5-point
+ * stencil with diag counting 1 per fluid neighbour and 1/theta per air neighbour                               */
+int mfs_density_apply2d(const int64_t gres[2], const void* v, void* out, int dt,
+                        const void* wx, const void* wy, int w_dt, const void* lphi, int lphi_dt, mfs_stream stream);
+/* replaces compute_displacement -- :141-152,227-231: dx[x,y], dy[x,y] for 1 <= x <= Nx-1, 1 <= y <= Ny-1 (the last
+ * cell included); every other entry of dx (Nx+1,Ny) and dy (Nx,Ny+1) is left alone                              */
+int mfs_density_displacement2d(const int64_t gres[2], double dt, const double cell_size[2],
+                               void* dx, void* dy, int d_dt, const void* pv, int pv_dt,
+                               const void* lphi, int lphi_dt, mfs_stream stream);
+/* replaces apply_displacement -- :171-195,233-238: px[:, axis] += bilinear sample of the face array d (shape dshape,
+ * samples at (index + grid_bias) * cell_size + bound_min, indices clamped to dshape); four separate additions
+ * into the stored value, so an fp32 px rounds after each                                                        */
+int mfs_density_advect2d(void* px, int px_dt, int64_t num_particles, const void* d, int d_dt,
+                         const int64_t dshape[2], const double bound_min[2], const double cell_size[2],
+                         const double grid_bias[2], int axis, mfs_stream stream);
+
+/* ------------------------------------------------------------------------- */
 /* Pressure, 2D (BASELINE config 1) -- reference solver/PressureCGSolver2D.py    */
 /* ------------------------------------------------------------------------- */
 /* replaces initialize_solver -- solver/PressureCGSolver2D.py:6-44,122-126 */
@@ -480,7 +518,13 @@ int mfs_pcg2d_create(mfs_pcg2d** out_host, const int64_t gres[2], int dt,
                      void* workspace, size_t workspace_bytes, mfs_stream stream);
 int mfs_pcg2d_destroy(mfs_pcg2d* h);
 int mfs_pcg2d_setup(mfs_pcg2d* h, const void* lphi, int lphi_dt, const void* wx, const void* wy, int w_dt);
+/* the same engine on DensityCGSolver2D's operator (solver/DensityCGSolver2D.py:85-139, loop :274-290); a later
+ * mfs_pcg2d_setup puts the engine back in pressure mode                                                      */
+int mfs_pcg2d_setup_density(mfs_pcg2d* h, const void* lphi, int lphi_dt, const void* wx, const void* wy, int w_dt);
 int mfs_pcg2d_bind(mfs_pcg2d* h, void* b, void* x, void* d, void* r, void* q);
+/* out = A v (the loop's stencil launch on caller vectors, in the mode the last setup chose; bit-identical to
+ * mfs_pressure_apply2d / mfs_density_apply2d, boundary cells of `out` untouched)                              */
+int mfs_pcg2d_apply(mfs_pcg2d* h, const void* v, void* out, mfs_stream stream);
 int mfs_pcg2d_solve(mfs_pcg2d* h, double tol, int64_t max_iter, int64_t check_every,
                     mfs_stream stream, int64_t* iters_host);
 int mfs_pcg2d_poll(mfs_pcg2d* h, mfs_stream stream, int64_t* iters_host, int* done_host,
@@ -608,6 +652,16 @@ int mfs_sdf_evaluate3d(const void* rb_d, int64_t num_bodies, const void* positio
                        void* sd, int sd_dt, void* vel, int vel_dt, mfs_stream stream);
 /* replaces project_kernel -- solver/sdf3D.py:241-258 (in place on position) */
 int mfs_sdf_project3d(const void* rb_d, int64_t num_bodies, void* position, int pos_dt, int64_t num_positions,
+                      mfs_stream stream);
+
+/* 2D -- reference solver/sdf2D.py.  rb_d: num_bodies x 8 x 3 float64 (generate_rb :221-252): row 0 = [type code,
+ * parameters] (code // 2: 0 sphere, 1 box; odd = flipped), rows 1-3 translation, rows 4-6 rotation, row 7 velocity.
+ * position / vel are (P,2) row-major.                                                                            */
+/* replaces evaluate_kernel -- solver/sdf2D.py:146-169 (the caller zeroes vel first, as evaluate() :190 does) */
+int mfs_sdf_evaluate2d(const void* rb_d, int64_t num_bodies, const void* position, int pos_dt, int64_t num_positions,
+                       void* sd, int sd_dt, void* vel, int vel_dt, mfs_stream stream);
+/* replaces project_kernel -- solver/sdf2D.py:171-183 (in place on position) */
+int mfs_sdf_project2d(const void* rb_d, int64_t num_bodies, void* position, int pos_dt, int64_t num_positions,
                       mfs_stream stream);
 
 #ifdef __cplusplus

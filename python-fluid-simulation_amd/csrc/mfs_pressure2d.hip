@@ -3,26 +3,12 @@
 // Reference: solver/PressureCGSolver2D.py.  The grids are tiny (64^2), so these
 // are plain one-thread-per-cell kernels in the reference's accumulation order; the
 // CG loop is the shared device-resident core (mfs_cg_core.h) with the 5-point
-// ghost-fluid operator applied straight from (lphi, wx, wy).
+// ghost-fluid operator applied straight from (lphi, wx, wy) (mfs_apply2d.h).  The same
+// engine runs DensityCGSolver2D's loop on the density operator (mfs_pcg2d_setup_density).
 #include "mfs_cg_core.h"
+#include "mfs_apply2d.h"
 
 namespace mfs {
-
-__device__ __forceinline__ double edge_in_fraction2(double l, double r) {  // SolidFractionCommon.py:4-16
-  const bool li = l < 0, ri = r < 0;
-  if (li && ri) return 1.0;
-  if (!li && !ri) return 0.0;
-  const double diff = -fabs(l - r);
-  return li ? l / diff : r / diff;
-}
-
-struct Grid2 {
-  int Nx, Ny;
-  __device__ int64_t c(int x, int y) const { return (int64_t)x * Ny + y; }
-  __device__ int64_t fx(int x, int y) const { return (int64_t)x * Ny + y; }
-  __device__ int64_t fy(int x, int y) const { return (int64_t)x * (Ny + 1) + y; }
-  __device__ int64_t dg(int i, int j) const { return (int64_t)i * (2 * Ny + 1) + j; }
-};
 
 // solver/PressureCGSolver2D.py:6-44
 __global__ void __launch_bounds__(256)
@@ -47,43 +33,6 @@ k_pressure_rhs2d(Grid2 g, double csx, double csy, const void* vx, const void* vy
   bv -= w * ldx(vy, vdt, g.fy(x, y)) / csy;
   if (w < 1) bv += w * ldx(sv, svdt, 2 * g.dg(2 * x + 1, 2 * y) + 1) / csy;
   stx(b, bdt, i, bv);
-}
-
-// solver/PressureCGSolver2D.py:46-100; also leaves per-block partials of v.out
-__global__ void __launch_bounds__(256)
-k_pressure_apply2d(Grid2 g, const void* v, void* out, int dt, const void* wx, const void* wy, int wdt,
-                   const void* lphi, int ldt, double* partial, const double* done_flag) {
-  if (done_flag && *done_flag != 0.0) return;
-  const int64_t n = (int64_t)g.Nx * g.Ny;
-  double acc = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int y = (int)(i % g.Ny), x = (int)(i / g.Ny);
-    if (x == 0 || x >= g.Nx - 1 || y == 0 || y >= g.Ny - 1) {
-      // never written, yet the reference's d.q sums the whole arrays: a shared buffer's stale q counts here
-      if (partial) acc += ldx(v, dt, i) * ldx(out, dt, i);
-      continue;
-    }
-    const double phi = ldx(lphi, ldt, i);
-    if (!(phi < 0)) { stx(out, dt, i, 0.0); continue; }
-    double val = 0.0, diag = 0.0;
-    auto tap = [&](int64_t nb, double w) {
-      const double nphi = ldx(lphi, ldt, nb);
-      if (nphi < 0) { val -= w * ldx(v, dt, nb); diag += w; }
-      else          { diag += w / fmin(1.0, fmax(0.01, phi / (phi - nphi))); }
-    };
-    tap(i + g.Ny, ldx(wx, wdt, g.fx(x + 1, y)));
-    tap(i - g.Ny, ldx(wx, wdt, g.fx(x, y)));
-    tap(i + 1, ldx(wy, wdt, g.fy(x, y + 1)));
-    tap(i - 1, ldx(wy, wdt, g.fy(x, y)));
-    const double vc = ldx(v, dt, i);
-    val += diag * vc;
-    stx(out, dt, i, val);
-    acc += vc * (dt == MFS_F32 ? (double)(float)val : val);
-  }
-  if (partial) {
-    const double tot = block_sum<256>(acc);
-    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
-  }
 }
 
 // solver/PressureCGSolver2D.py:102-120
@@ -121,17 +70,17 @@ struct mfs_pcg2d {
   const void *lphi, *wx, *wy;
   int ldt, wdt;
   int grid;
+  bool density;   // the stencil launch applies the density operator (mfs_pcg2d_setup_density) instead of the pressure one
 };
 
-static int check_gres2(const int64_t gres[2]) {
-  MFS_REQUIRE(gres != nullptr, "gres is null");
-  MFS_REQUIRE(gres[0] >= 1 && gres[1] >= 1 && gres[0] <= 65536 && gres[1] <= 65536, "grid resolution out of range");
-  return MFS_OK;
-}
-
 static int apply2d(mfs_pcg2d* h, const void* v, void* out, bool use_done, hipStream_t st) {
-  hipLaunchKernelGGL(k_pressure_apply2d, dim3(h->grid), dim3(256), 0, st, h->g, v, out, h->dt, h->wx, h->wy, h->wdt,
-                     h->lphi, h->ldt, h->c.part_dq, use_done ? h->c.scal + S_DONE : nullptr);
+  const double* done = use_done ? h->c.scal + S_DONE : nullptr;
+  if (h->density)
+    hipLaunchKernelGGL(k_apply2d<true>, dim3(h->grid), dim3(256), 0, st, h->g, v, out, h->dt, h->wx, h->wy, h->wdt,
+                       h->lphi, h->ldt, h->c.part_dq, done);
+  else
+    hipLaunchKernelGGL(k_apply2d<false>, dim3(h->grid), dim3(256), 0, st, h->g, v, out, h->dt, h->wx, h->wy, h->wdt,
+                       h->lphi, h->ldt, h->c.part_dq, done);
   MFS_LAUNCH_CHECK();
   h->c.n_part_dq = h->grid;
   return MFS_OK;
@@ -158,7 +107,7 @@ int mfs_pressure_apply2d(const int64_t gres[2], const void* v, void* out, int dt
   MFS_REQUIRE(v && out && wx && wy && lphi && v != out, "null / aliased array");
   MFS_REQUIRE(dtype_ok(dt) && dtype_ok(w_dt) && dtype_ok(lphi_dt), "dtype");
   Grid2 g{(int)gres[0], (int)gres[1]};
-  hipLaunchKernelGGL(k_pressure_apply2d, dim3(cdiv(gres[0] * gres[1], 256)), dim3(256), 0, (hipStream_t)stream, g, v,
+  hipLaunchKernelGGL(k_apply2d<false>, dim3(cdiv(gres[0] * gres[1], 256)), dim3(256), 0, (hipStream_t)stream, g, v,
                      out, dt, wx, wy, w_dt, lphi, lphi_dt, (double*)nullptr, (const double*)nullptr);
   MFS_LAUNCH_CHECK();
   return MFS_OK;
@@ -195,6 +144,7 @@ int mfs_pcg2d_create(mfs_pcg2d** out, const int64_t gres[2], int dt, void* works
   if (int e = core_init(h->c, dt, gres[0] * gres[1])) { delete h; return e; }
   core_carve(h->c, (char*)workspace);
   h->lphi = h->wx = h->wy = nullptr;
+  h->density = false;
   h->grid = std::max(1, std::min(h->c.grid_vec, cdiv(gres[0] * gres[1], 256)));
   if (hipMemsetAsync(workspace, 0, mfs_pcg2d_workspace_bytes(gres, dt), (hipStream_t)stream) != hipSuccess) {
     set_error("hipMemsetAsync(workspace) failed");
@@ -217,7 +167,22 @@ int mfs_pcg2d_setup(mfs_pcg2d* h, const void* lphi, int lphi_dt, const void* wx,
   MFS_REQUIRE(h && lphi && wx && wy, "null argument");
   MFS_REQUIRE(dtype_ok(lphi_dt) && dtype_ok(w_dt), "dtype");
   h->lphi = lphi; h->ldt = lphi_dt; h->wx = wx; h->wy = wy; h->wdt = w_dt;
+  h->density = false;
   return MFS_OK;
+}
+
+// solver/DensityCGSolver2D.py:274-290: the same loop on the density operator (matvecmul_kernel :85-139)
+int mfs_pcg2d_setup_density(mfs_pcg2d* h, const void* lphi, int lphi_dt, const void* wx, const void* wy, int w_dt) {
+  if (int e = mfs_pcg2d_setup(h, lphi, lphi_dt, wx, wy, w_dt)) return e;
+  h->density = true;
+  return MFS_OK;
+}
+
+// the loop's stencil launch on caller vectors, in the mode the last setup chose (boundary cells of `out` untouched)
+int mfs_pcg2d_apply(mfs_pcg2d* h, const void* v, void* out, mfs_stream stream) {
+  MFS_REQUIRE(h && h->lphi, "engine not set up");
+  MFS_REQUIRE(v && out && v != out, "null / aliased array");
+  return apply2d(h, v, out, false, (hipStream_t)stream);
 }
 
 int mfs_pcg2d_bind(mfs_pcg2d* h, void* b, void* x, void* d, void* r, void* q) {

@@ -169,6 +169,12 @@ SIGNATURES = {
     "mfs_density_apply3d": (_i, [_pi64, _p, _p, _i, _p, _p, _p, _i, _p, _i, _p]),
     "mfs_density_displacement3d": (_i, [_pi64, _d, _pd, _p, _p, _p, _i, _p, _i, _p, _i, _p]),
     "mfs_density_advect3d": (_i, [_p, _i, _i64, _p, _i, _pi64, _pd, _pd, _pd, _i, _p]),
+    "mfs_density_splat2d": (_i, [_pi64, _pd, _pd, _p, _i, _p, _i, _d, _i64, _p, _p, _i, _p]),
+    "mfs_density_fix_volume2d": (_i, [_pi64, _pd, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p]),
+    "mfs_density_rhs2d": (_i, [_pi64, _d, _d, _pd, _p, _p, _i, _p, _i, _p, _p, _i, _p, _i, _p]),
+    "mfs_density_apply2d": (_i, [_pi64, _p, _p, _i, _p, _p, _i, _p, _i, _p]),
+    "mfs_density_displacement2d": (_i, [_pi64, _d, _pd, _p, _p, _i, _p, _i, _p, _i, _p]),
+    "mfs_density_advect2d": (_i, [_p, _i, _i64, _p, _i, _pi64, _pd, _pd, _pd, _i, _p]),
     "mfs_p2g_scatter3d": (_i, [_pi64, _pd, _pd, _pd, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i64, _p, _p, _i, _p]),
     "mfs_p2g_normalize3d": (_i, [_i64, _p, _p, _i, _p]),
     "mfs_particle_tiles3d": (_i64, [_pi64]),
@@ -182,6 +188,8 @@ SIGNATURES = {
     "mfs_fluid_volume3d": (_i, [_pi64, _pd, _pd, _p, _i, _d, _i64, _p, _i, _p]),
     "mfs_sdf_evaluate3d": (_i, [_p, _i64, _p, _i, _i64, _p, _i, _p, _i, _p]),
     "mfs_sdf_project3d": (_i, [_p, _i64, _p, _i, _i64, _p]),
+    "mfs_sdf_evaluate2d": (_i, [_p, _i64, _p, _i, _i64, _p, _i, _p, _i, _p]),
+    "mfs_sdf_project2d": (_i, [_p, _i64, _p, _i, _i64, _p]),
     "mfs_pressure_rhs2d": (_i, [_pi64, _pd, _p, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _i, _p]),
     "mfs_pressure_apply2d": (_i, [_pi64, _p, _p, _i, _p, _p, _i, _p, _i, _p]),
     "mfs_pressure_update2d": (_i, [_pi64, _pd, _p, _p, _i, _p, _i, _p, _p, _i, _p, _i, _p, _i, _p]),
@@ -189,7 +197,9 @@ SIGNATURES = {
     "mfs_pcg2d_create": (_i, [C.POINTER(_p), _pi64, _i, _p, _sz, _p]),
     "mfs_pcg2d_destroy": (_i, [_p]),
     "mfs_pcg2d_setup": (_i, [_p, _p, _i, _p, _p, _i]),
+    "mfs_pcg2d_setup_density": (_i, [_p, _p, _i, _p, _p, _i]),
     "mfs_pcg2d_bind": (_i, [_p, _p, _p, _p, _p, _p]),
+    "mfs_pcg2d_apply": (_i, [_p, _p, _p, _p]),
     "mfs_pcg2d_solve": (_i, [_p, _d, _i64, _i64, _p, _pi64]),
     "mfs_pcg2d_poll": (_i, [_p, _p, _pi64, _pint, _pd, _pd, _pd]),
     "mfs_pcg2d_history": (_i64, [_p, _pd, _i64, _p]),

@@ -518,3 +518,117 @@ def particle_stress_scene_3d(gres=(100, 44, 67), seed=0, *, bulk=300000, per_wal
     return dict(gres=tuple(int(v) for v in N), bound_min=bmin, bound_size=bsz, cell_size=cs, gdx=float(cs.min()),
                 px=X, pm=pm, pv=pv, pcx=aff[0], pcy=aff[1], pcz=aff[2], pvol=pvol,
                 lone=int(np.nonzero(order == n - 1)[0][0]))
+
+
+# ----------------------------------------------------------------------------
+# 2D density scene (reference solver/DensityCGSolver2D.py, solver/sdf2D.py)
+# ----------------------------------------------------------------------------
+def _rb2(kind, params, flip, centre, angle, vel=(0.0, 0.0)):
+    """one (8,3) body block in the packed layout of solver/sdf2D.py: row 0 = [type code, parameters], rows 1-3
+    translation, rows 4-6 rotation, row 7 velocity"""
+    rb = np.zeros((8, 3))
+    rb[0, 0] = {"sphere": 0, "box": 2}[kind] + (1 if flip else 0)
+    rb[0, 1:1 + len(params)] = params
+    rb[1:4] = np.identity(3)
+    rb[1:3, 2] = centre
+    rb[4:7] = np.identity(3)
+    if angle:
+        rad = angle * np.pi / 180
+        c, s = np.cos(rad), np.sin(rad)
+        rb[4:6, :2] = ((c, -s), (s, c))
+    rb[7, :2] = vel
+    return rb
+
+
+def _sdf2(rb_d, X, Y):
+    """signed distance to the closest body and that body's velocity where the distance is <= 0 (input generator for
+    sphi / sv; sign convention of solver/sdf2D.py: a flipped body is solid OUTSIDE)"""
+    sd = np.full(np.broadcast(X, Y).shape, 100.0)
+    vel = np.zeros(sd.shape + (2,))
+    win = np.zeros(sd.shape, dtype=np.int64)
+    for i, rb in enumerate(rb_d):
+        T, R = rb[1:3, 2], rb[4:6, :2]
+        if rb[0, 0] // 2 == 0:
+            d = np.sqrt((X - T[0]) ** 2 + (Y - T[1]) ** 2) - rb[0, 1]
+        else:
+            bx = R[0, 0] * (X - T[0]) + R[1, 0] * (Y - T[1])
+            by = R[0, 1] * (X - T[0]) + R[1, 1] * (Y - T[1])
+            ex, ey = np.abs(bx) - rb[0, 1] / 2, np.abs(by) - rb[0, 2] / 2
+            d = np.sqrt(np.maximum(ex, 0) ** 2 + np.maximum(ey, 0) ** 2) + np.minimum(np.maximum(ex, ey), 0)
+        if rb[0, 0] % 2:
+            d = -d
+        closer = d < sd
+        sd = np.where(closer, d, sd)
+        win = np.where(closer, i, win)
+    inside = sd <= 0
+    vel[inside] = np.asarray(rb_d)[win[inside], 7, :2]
+    return sd, vel
+
+
+def density_scene_2d(gres, seed=0, *, bound_min=(-0.2, 0.1), bound_size=(1.0, 1.0), per_cell=4, px_dtype=np.float64,
+                     rho0=1000.0, dt=1.0 / 300.0, wall_particles=8):
+    """Inputs of DensityCGSolver2D.solve and of sdf2D.evaluate / project.  numpy only.
+
+    Bodies (`bodies`: what to hand to sdf2D.generate_rb / set_vel_rb; `rb_d`: the packed (3,8,3) array): a flipped box
+    1.5 cells inside the bounds (the container), a box rotated by 30 degrees that moves, and a sphere.  `sphi`, `sv` are
+    their signed distance / velocity on the doubled grid.  The liquid is a pool with a wavy surface: `lphi` at cell
+    centres (a few surface cells sit a hair below zero, so the operator's theta clamp 0.01 is hit), `lvol` the pool's
+    share of every doubled-grid node's sub-cell.  Particles: `per_cell` jittered per liquid cell, except a band of
+    columns filled three times over (density fraction above its clamp 1.5) and a band left empty (fraction below 0.5
+    at its edges, the `cell_mass < 1e-10` branch inside); `wall_particles` more within half a cell of each of the four
+    bounds (index clamps of the scatter and the gathers)."""
+    Nx, Ny = (int(g) for g in gres)
+    bmin = np.asarray(bound_min, np.float64)
+    size = np.asarray(bound_size, np.float64)
+    cs = size / np.array([Nx, Ny], np.float64)
+    ctr = bmin + 0.5 * size
+    bodies = [
+        dict(name="tank", rbparam=["box", float(size[0] - 3.0 * cs[0]), float(size[1] - 3.0 * cs[1])], flip=True,
+             center=[float(ctr[0]), float(ctr[1])], angle=0, vel=[0.0, 0.0]),
+        dict(name="bar", rbparam=["box", float(0.30 * size[0]), float(0.08 * size[1])], flip=False,
+             center=[float(bmin[0] + 0.33 * size[0]), float(bmin[1] + 0.30 * size[1])], angle=30, vel=[0.3, -0.2]),
+        dict(name="ball", rbparam=["sphere", float(0.11 * min(size))], flip=False,
+             center=[float(bmin[0] + 0.72 * size[0]), float(bmin[1] + 0.36 * size[1])], angle=0, vel=[0.0, 0.0]),
+    ]
+    rb_d = np.stack([_rb2(b["rbparam"][0], b["rbparam"][1:], b["flip"], b["center"], b["angle"], b["vel"])
+                     for b in bodies])
+    X = (bmin[0] + np.arange(2 * Nx + 1) * 0.5 * cs[0])[:, None]
+    Y = (bmin[1] + np.arange(2 * Ny + 1) * 0.5 * cs[1])[None, :]
+    sphi, sv = _sdf2(rb_d, X, Y)
+
+    def surface(x):
+        return bmin[1] + size[1] * (0.58 + 0.04 * np.sin(7.0 * (x - bmin[0]) / size[0]))
+
+    cx = bmin[0] + (np.arange(Nx) + 0.5) * cs[0]
+    cy = bmin[1] + (np.arange(Ny) + 0.5) * cs[1]
+    lphi = cy[None, :] - surface(cx)[:, None]
+    top = np.clip((lphi < 0).sum(axis=1) - 1, 1, Ny - 2)          # topmost liquid cell of every column
+    cols = np.arange(Nx)
+    hair = (cols % 5 == 2) & (cols > 0) & (cols < Nx - 1)
+    lphi[cols[hair], top[hair]] = -1e-4 * cs[1]
+    # the pool's share of the sub-cell (0.5 cs)^2 around every doubled-grid node, none of it inside a solid
+    lvol = np.clip(surface(X) - (Y - 0.25 * cs[1]), 0.0, 0.5 * cs[1]) * (0.5 * cs[0]) * (sphi > 0)
+
+    rng = np.random.default_rng(seed + 2000)
+    liquid = (lphi < 0) & (sphi[1::2, 1::2] > 0)
+    full = (cols >= int(0.30 * Nx)) & (cols < int(0.30 * Nx) + 3)
+    empty = (cols >= int(0.55 * Nx)) & (cols < int(0.55 * Nx) + 4)
+    count = liquid * (per_cell * np.where(full, 3, 1) * ~empty)[:, None]
+    ci, cj = np.nonzero(count)
+    rep = count[ci, cj]
+    ci, cj = np.repeat(ci, rep), np.repeat(cj, rep)
+    pos = np.stack([bmin[0] + (ci + rng.uniform(0, 1, len(ci))) * cs[0],
+                    bmin[1] + (cj + rng.uniform(0, 1, len(cj))) * cs[1]], axis=1)
+    k = int(wall_particles)
+    u, v = rng.uniform(0.02, 0.48, (4, k)), rng.uniform(0.05, 0.95, (4, k))
+    walls = np.concatenate([
+        np.stack([bmin[0] + u[0] * cs[0], bmin[1] + v[0] * size[1]], axis=1),
+        np.stack([bmin[0] + size[0] - u[1] * cs[0], bmin[1] + v[1] * size[1]], axis=1),
+        np.stack([bmin[0] + v[2] * size[0], bmin[1] + u[2] * cs[1]], axis=1),
+        np.stack([bmin[0] + v[3] * size[0], bmin[1] + size[1] - u[3] * cs[1]], axis=1)])
+    pos = np.concatenate([pos, walls])
+    pvol = float(np.prod(cs)) / per_cell
+    pm = rho0 * pvol * (1.0 + 0.1 * rng.standard_normal(len(pos)))
+    return dict(gres=(Nx, Ny), bound_min=tuple(float(b) for b in bmin), bound_size=tuple(float(v) for v in size),
+                cell_size=tuple(float(c) for c in cs), bodies=bodies, rb_d=rb_d, sphi=sphi, sv=sv, lphi=lphi, lvol=lvol,
+                px=pos.astype(px_dtype), pm=pm, pvol=pvol, rho0=float(rho0), dt=float(dt))
