@@ -664,6 +664,48 @@ int mfs_sdf_evaluate2d(const void* rb_d, int64_t num_bodies, const void* positio
 int mfs_sdf_project2d(const void* rb_d, int64_t num_bodies, void* position, int pos_dt, int64_t num_positions,
                       mfs_stream stream);
 
+/* ------------------------------------------------------------------------- */
+/* The 2D time step: particle <-> grid transfers and grid kernels (csrc/mfs_notebook2d.hip) */
+/* ------------------------------------------------------------------------- */
+/* The reference has no 2D driver.  These are the 3D entry points above one dimension down: the same float32 locals
+ * and the same order of operations with the z factor / z terms removed, so a 3D run whose particles lie on a
+ * cell-centre plane and whose fields do not vary in z gives the bits of the 2D run on that plane.  Particle arrays:
+ * px, pv, pca are (P,2) row-major, pm is (P).  Face arrays: x (Nx+1,Ny), y (Nx,Ny+1); doubled grid (2Nx+1,2Ny+1);
+ * sv (2Nx+1,2Ny+1,2).  num_particles == 0 returns MFS_OK without a launch.  p2g's division is dimension-free:
+ * mfs_p2g_normalize3d.                                                                                          */
+/* mfs_p2g_scatter3d in 2D: APIC scatter of mass and momentum of component `axis` (0, 1) to its face array; four
+ * corners, indices clamped to gres - 1                                                                          */
+int mfs_p2g_scatter2d(const int64_t gres[2], const double bound_min[2], const double cell_size[2],
+                      const double grid_bias[2], int axis, const void* px, int px_dt, const void* pm, int pm_dt,
+                      const void* pv, int pv_dt, const void* pca, int pca_dt, int64_t num_particles,
+                      void* gm, void* gv, int g_dt, mfs_stream stream);
+/* mfs_g2p_gather3d in 2D: pv[:, axis] and the affine row pca[:, 0:2] from the face array gv */
+int mfs_g2p_gather2d(const int64_t gres[2], const double bound_min[2], const double cell_size[2],
+                     const double grid_bias[2], int axis, const void* px, int px_dt, void* pv, int pv_dt,
+                     void* pca, int pca_dt, int64_t num_particles, const void* gv, int g_dt, mfs_stream stream);
+/* mfs_fluid_levelset3d in 2D: phi = min(phi, |cell centre - x| - radius) over the 5^2 cells around each particle.
+ * The caller pre-fills phi.                                                                                     */
+int mfs_fluid_levelset2d(const int64_t gres[2], const double bound_min[2], const double cell_size[2], double radius,
+                         const void* px, int px_dt, int64_t num_particles, void* phi, int phi_dt, mfs_stream stream);
+/* mfs_fluid_volume3d in 2D: bilinear splat of the particle volume (an area) onto the nodes of `gvol` (shape vres,
+ * spacing cell_size), then min(., cell_size[0] * cell_size[1]).  The caller zeroes gvol first.                  */
+int mfs_fluid_volume2d(const int64_t vres[2], const double bound_min[2], const double cell_size[2],
+                       const void* px, int px_dt, double pvol, int64_t num_particles, void* gvol, int g_dt,
+                       mfs_stream stream);
+/* mfs_grid_extrapolate3d in 2D: num_iter Jacobi sweeps of the 4-neighbour average into interior faces with
+ * mass <= 0; a face filled by one sweep is valid for the next; a sweep reads the previous sweep's values only
+ * (ping-pong buffers in `workspace`, 256-byte aligned); array-boundary faces are untouched                      */
+size_t mfs_grid_extrapolate2d_workspace_bytes(const int64_t gres[2], int v_dt);
+int mfs_grid_extrapolate2d(const int64_t gres[2], int num_iter, void* vx, void* vy, int v_dt,
+                           const void* mx, const void* my, int m_dt,
+                           void* workspace, size_t workspace_bytes, mfs_stream stream);
+/* mfs_grid_boundary_condition3d in 2D: the free-slip corrections dv_x, dv_y (the caller adds them); 0 on
+ * array-boundary faces and where sphi / dx >= 1                                                                 */
+int mfs_grid_boundary_condition2d(const int64_t gres[2], const void* gvx, const void* gvy, int v_dt,
+                                  const void* gmx, const void* gmy, int m_dt,
+                                  const void* sphi, int sphi_dt, const void* sv, int sv_dt, double dx,
+                                  void* dvx, void* dvy, int dv_dt, mfs_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

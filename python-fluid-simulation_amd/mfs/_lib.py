@@ -216,6 +216,13 @@ SIGNATURES = {
     "mfs_vcg2d_solve": (_i, [_p, _d, _i64, _i64, _p, _pi64]),
     "mfs_vcg2d_poll": (_i, [_p, _p, _pi64, _pint, _pd, _pd, _pd]),
     "mfs_vcg2d_history": (_i64, [_p, _pd, _i64, _p]),
+    "mfs_p2g_scatter2d": (_i, [_pi64, _pd, _pd, _pd, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i64, _p, _p, _i, _p]),
+    "mfs_g2p_gather2d": (_i, [_pi64, _pd, _pd, _pd, _i, _p, _i, _p, _i, _p, _i, _i64, _p, _i, _p]),
+    "mfs_fluid_levelset2d": (_i, [_pi64, _pd, _pd, _d, _p, _i, _i64, _p, _i, _p]),
+    "mfs_fluid_volume2d": (_i, [_pi64, _pd, _pd, _p, _i, _d, _i64, _p, _i, _p]),
+    "mfs_grid_extrapolate2d_workspace_bytes": (_sz, [_pi64, _i]),
+    "mfs_grid_extrapolate2d": (_i, [_pi64, _i, _p, _p, _i, _p, _p, _i, _p, _sz, _p]),
+    "mfs_grid_boundary_condition2d": (_i, [_pi64, _p, _p, _i, _p, _p, _i, _p, _i, _p, _i, _d, _p, _p, _i, _p]),
 }
 
 _lib = None

@@ -455,6 +455,46 @@ def particle_scene_3d(gres, seed=0, *, per_cell=3, bound_min=(-0.3, 0.0, -0.3)):
                 gdx=gdx, px=px, pm=pm, pv=pv, pcx=aff[0], pcy=aff[1], pcz=aff[2], pvol=float(pvol))
 
 
+def particle_scene_2d(gres, seed=0, *, per_cell=4, bound_min=(-0.3, 0.0), device=None):
+    """Inputs of the 2D particle <-> grid transfers (notebook_kernels2d), in the style of `particle_scene_3d`: jittered
+    particles in a block in the lower part of a box of square cells of size gdx; particles pressed against each of the
+    four walls (within 0.7 cell inside); a few outside the domain (up to 1.5 cells), so that the index clamps fire on both
+    sides of both axes; one particle exactly at `bound_min`; a shuffled order; velocities and affine rows random.
+    `bound_min` / `bound_size` are float32 arrays and `cell_size` float64, as the containers hold them.  numpy arrays, or
+    torch tensors on `device` for the particle arrays when one is given."""
+    Nx, Ny = (int(g) for g in gres)
+    gdx = 0.05
+    N = np.array([Nx, Ny], np.int64)
+    bmin = np.asarray(bound_min, np.float32)
+    bsz = (N * gdx).astype(np.float32)
+    cs = bsz / N
+    size = N * cs
+    rng = np.random.default_rng(seed + 4000)
+    n = max(8, per_cell * Nx * Ny // 2)
+    block = rng.uniform([0.8, 0.8], [Nx - 0.8, max(1.0, 0.55 * Ny)], size=(n, 2))          # in cells
+    k = max(4, n // 40)
+    parts = [block]
+    for a in range(2):
+        for side in (0, 1):
+            q = rng.uniform([0.0, 0.0], N.astype(np.float64), size=(2 * k, 2))
+            d = np.concatenate([rng.uniform(0.0, 0.7, k), rng.uniform(-1.5, 0.0, k)])      # pressed against / outside
+            q[:, a] = d if side == 0 else N[a] - d
+            parts.append(q)
+    X = np.concatenate(parts) * cs + bmin.astype(np.float64)
+    X = np.concatenate([X, bmin.astype(np.float64)[None]])
+    X = X[rng.permutation(len(X))]
+    P = len(X)
+    pvol = gdx ** 2 / per_cell
+    out = dict(px=X, pm=1000.0 * pvol * (1.0 + 0.1 * rng.standard_normal(P)), pv=rng.standard_normal((P, 2)),
+               pcx=2.0 * rng.standard_normal((P, 2)), pcy=2.0 * rng.standard_normal((P, 2)))
+    if device is not None:
+        import torch
+        out = {k_: torch.as_tensor(v, device=device) for k_, v in out.items()}
+    out.update(gres=(Nx, Ny), bound_min=bmin, bound_size=bsz, cell_size=cs, gdx=gdx, pvol=float(pvol),
+               size=tuple(float(v) for v in size))
+    return out
+
+
 def particle_stress_scene_3d(gres=(100, 44, 67), seed=0, *, bulk=300000, per_wall=5000, bound_min=(-0.3, 0.0, -0.3),
                              bound_size=(1.2, 0.5, 0.9)):
     """A particle set built to reach what `particle_scene_3d` and a mesh-ordered block never do in the particle <-> grid
