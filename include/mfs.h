@@ -650,6 +650,14 @@ int mfs_fluid_volume3d(const int64_t vres[3], const double bound_min[3], const d
 /* replaces evaluate_kernel -- solver/sdf3D.py:218-239 (the caller zeroes vel first, as evaluate() :266 does) */
 int mfs_sdf_evaluate3d(const void* rb_d, int64_t num_bodies, const void* position, int pos_dt, int64_t num_positions,
                        void* sd, int sd_dt, void* vel, int vel_dt, mfs_stream stream);
+/* evaluate_kernel on the nodes of a regular grid, for solids that move (no reference counterpart).  The position of
+ * index i along an axis is get_grid_pos' (notebook code cell 9): (double)(float)bound_min + (double)((float)i +
+ * (float)bias) * cell_size, multiply and add rounded separately.  sd: res[0] x res[1] x res[2] in C order, vel the same
+ * with 3 components last; EVERY vel element is written: 0 where sd > 0 (or no bodies), else the winning body's row 9 --
+ * plus w x (pos - T) when rb_w (num_bodies x 3 float64, rad/s; may be null = all zero) is given.  Extents up to 2^30. */
+int mfs_sdf_evaluate_grid3d(const void* rb_d, int64_t num_bodies, const void* rb_w, const int64_t res[3],
+                            const double bound_min[3], const double bias[3], const double cell_size[3], void* sd,
+                            int sd_dt, void* vel, int vel_dt, mfs_stream stream);
 /* replaces project_kernel -- solver/sdf3D.py:241-258 (in place on position) */
 int mfs_sdf_project3d(const void* rb_d, int64_t num_bodies, void* position, int pos_dt, int64_t num_positions,
                       mfs_stream stream);
@@ -660,6 +668,11 @@ int mfs_sdf_project3d(const void* rb_d, int64_t num_bodies, void* position, int 
 /* replaces evaluate_kernel -- solver/sdf2D.py:146-169 (the caller zeroes vel first, as evaluate() :190 does) */
 int mfs_sdf_evaluate2d(const void* rb_d, int64_t num_bodies, const void* position, int pos_dt, int64_t num_positions,
                        void* sd, int sd_dt, void* vel, int vel_dt, mfs_stream stream);
+/* mfs_sdf_evaluate_grid3d one dimension down: sd res[0] x res[1], vel with 2 components last; rb_w: num_bodies float64
+ * (may be null); the surface velocity is (v0 - w r1, v1 + w r0) with r = pos - T.                                  */
+int mfs_sdf_evaluate_grid2d(const void* rb_d, int64_t num_bodies, const void* rb_w, const int64_t res[2],
+                            const double bound_min[2], const double bias[2], const double cell_size[2], void* sd,
+                            int sd_dt, void* vel, int vel_dt, mfs_stream stream);
 /* replaces project_kernel -- solver/sdf2D.py:171-183 (in place on position) */
 int mfs_sdf_project2d(const void* rb_d, int64_t num_bodies, void* position, int pos_dt, int64_t num_positions,
                       mfs_stream stream);

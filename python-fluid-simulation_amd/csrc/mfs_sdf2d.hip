@@ -150,6 +150,56 @@ k_sdf_evaluate2d(const double* __restrict__ rb_d, int nrb, const void* position,
   }
 }
 
+// evaluate_kernel on the nodes of a regular grid (moving bodies: one solid level set per step): the position comes from
+// the index by get_grid_pos' rule -- bound_min(f32) + (f32 index + f32 bias) * cell_size in float64, multiply and add
+// rounded separately -- and EVERY vel element is written (0 outside the bodies).  rb_w (n), optional: angular velocities;
+// the winning body's surface velocity is then v + w x (pos - T): (v0 - w r1, v1 + w r0), every operation rounded on its own.
+struct GridArgs2 {
+  int64_t n1, total;             // extent of the inner axis, number of points
+  double bmin[2];                // bound_min, already rounded to float32
+  float bias[2];
+  double cs[2];
+};
+
+__global__ void __launch_bounds__(256)
+k_sdf_evaluate_grid2d(const double* __restrict__ rb_d, int nrb, const double* __restrict__ rb_w, GridArgs2 a, void* sd,
+                      int sdt, void* vel, int vdt) {
+  const int64_t base = (int64_t)blockIdx.x * 256;       // wave-uniform: the 64-bit division is per block ...
+  const int64_t p = base + threadIdx.x;
+  if (p >= a.total) return;
+  int64_t i0 = base / a.n1;
+  uint32_t i1 = (uint32_t)(base - i0 * a.n1) + threadIdx.x;    // ... and per thread 32-bit (extents <= 2^30)
+  const uint32_t q1 = i1 / (uint32_t)a.n1;
+  i1 -= q1 * (uint32_t)a.n1;
+  i0 += q1;
+  const double pos[2] = {a.bmin[0] + (double)((float)i0 + a.bias[0]) * a.cs[0],
+                         a.bmin[1] + (double)((float)i1 + a.bias[1]) * a.cs[1]};
+  double min_sd = 100.0;
+  int idx = 0;
+  for (int i = 0; i < nrb; ++i) {
+    const Rb2 r = rb2_load(rb_d, i);
+    const int kind = (int)floor(r.p[0] / 2);
+    double d = min_sd;                        // unknown kinds leave the minimum alone
+    if (kind == 0) d = sphere_eval2(r, pos);
+    else if (kind == 1) d = box_eval2(r, pos);
+    if (d < min_sd) { min_sd = d; idx = i; }
+  }
+  stx(sd, sdt, p, min_sd);
+  double v[2] = {0.0, 0.0};
+  if (min_sd <= 0 && nrb > 0) {
+    const Rb2 r = rb2_load(rb_d, idx);
+    v[0] = r.vel[0];
+    v[1] = r.vel[1];
+    if (rb_w) {
+      const double w = rb_w[idx];
+      const double d[2] = {pos[0] - r.T[0], pos[1] - r.T[1]};
+      v[0] = r.vel[0] - w * d[1];
+      v[1] = r.vel[1] + w * d[0];
+    }
+  }
+  for (int k = 0; k < 2; ++k) stx(vel, vdt, 2 * p + k, v[k]);
+}
+
 // project_kernel :171-183 -- every body in turn, each on the position the previous one left
 __global__ void __launch_bounds__(256)
 k_sdf_project2d(const double* __restrict__ rb_d, int nrb, void* position, int pdt, int64_t P) {
@@ -171,6 +221,10 @@ k_sdf_project2d(const double* __restrict__ rb_d, int nrb, void* position, int pd
 
 using namespace mfs;
 
+// evaluate_grid: per-thread index arithmetic is 32-bit within a row, the flat index 64-bit; one launch of 256-thread blocks
+static const int64_t kGridMaxExtent2 = (int64_t)1 << 30;
+static const int64_t kGridMaxPoints2 = (int64_t)0x7fffffff * 256;
+
 extern "C" {
 
 int mfs_sdf_evaluate2d(const void* rb_d, int64_t num_bodies, const void* position, int pos_dt, int64_t num_positions,
@@ -181,6 +235,30 @@ int mfs_sdf_evaluate2d(const void* rb_d, int64_t num_bodies, const void* positio
   if (num_positions == 0) return MFS_OK;
   hipLaunchKernelGGL(k_sdf_evaluate2d, dim3(cdiv(num_positions, 256)), dim3(256), 0, (hipStream_t)stream,
                      (const double*)rb_d, (int)num_bodies, position, pos_dt, num_positions, sd, sd_dt, vel, vel_dt);
+  MFS_LAUNCH_CHECK();
+  return MFS_OK;
+}
+
+int mfs_sdf_evaluate_grid2d(const void* rb_d, int64_t num_bodies, const void* rb_w, const int64_t res[2],
+                            const double bound_min[2], const double bias[2], const double cell_size[2], void* sd,
+                            int sd_dt, void* vel, int vel_dt, mfs_stream stream) {
+  MFS_REQUIRE(num_bodies >= 0 && num_bodies <= 4096 && (num_bodies == 0 || rb_d), "rigid bodies");
+  MFS_REQUIRE(res && bound_min && bias && cell_size, "null grid description");
+  MFS_REQUIRE(res[0] >= 0 && res[1] >= 0 && res[0] <= kGridMaxExtent2 && res[1] <= kGridMaxExtent2, "grid extents");
+  MFS_REQUIRE(dtype_ok(sd_dt) && dtype_ok(vel_dt), "dtype");
+  if (res[0] == 0 || res[1] == 0) return MFS_OK;
+  MFS_REQUIRE(res[0] <= kGridMaxPoints2 / res[1], "grid too large for one launch");
+  MFS_REQUIRE(sd && vel, "output arrays");
+  GridArgs2 a;
+  a.n1 = res[1];
+  a.total = res[0] * res[1];
+  for (int k = 0; k < 2; ++k) {
+    a.bmin[k] = (double)(float)bound_min[k];
+    a.bias[k] = (float)bias[k];
+    a.cs[k] = cell_size[k];
+  }
+  hipLaunchKernelGGL(k_sdf_evaluate_grid2d, dim3(cdiv(a.total, 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const double*)rb_d, (int)num_bodies, (const double*)rb_w, a, sd, sd_dt, vel, vel_dt);
   MFS_LAUNCH_CHECK();
   return MFS_OK;
 }

@@ -187,8 +187,10 @@ SIGNATURES = {
     "mfs_fluid_levelset3d": (_i, [_pi64, _pd, _pd, _d, _p, _i, _i64, _p, _i, _p]),
     "mfs_fluid_volume3d": (_i, [_pi64, _pd, _pd, _p, _i, _d, _i64, _p, _i, _p]),
     "mfs_sdf_evaluate3d": (_i, [_p, _i64, _p, _i, _i64, _p, _i, _p, _i, _p]),
+    "mfs_sdf_evaluate_grid3d": (_i, [_p, _i64, _p, _pi64, _pd, _pd, _pd, _p, _i, _p, _i, _p]),
     "mfs_sdf_project3d": (_i, [_p, _i64, _p, _i, _i64, _p]),
     "mfs_sdf_evaluate2d": (_i, [_p, _i64, _p, _i, _i64, _p, _i, _p, _i, _p]),
+    "mfs_sdf_evaluate_grid2d": (_i, [_p, _i64, _p, _pi64, _pd, _pd, _pd, _p, _i, _p, _i, _p]),
     "mfs_sdf_project2d": (_i, [_p, _i64, _p, _i, _i64, _p]),
     "mfs_pressure_rhs2d": (_i, [_pi64, _pd, _p, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _i, _p]),
     "mfs_pressure_apply2d": (_i, [_pi64, _p, _p, _i, _p, _p, _i, _p, _i, _p]),

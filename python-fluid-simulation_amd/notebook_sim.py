@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 import notebook_kernels as K
+from mfs.motion import BodyKinematics
 from solver import sdf3D as sdf
 from solver.CGSolverBuffer import CGSolverBuffer
 from solver.DensityCGSolver3D import DensityCGSolver3D, SlabDensityCGSolver3D
@@ -42,9 +43,11 @@ class NotebookSimulation:
     px: (P,3) float64 particle positions; pdx: particle spacing (mass = rho * pdx^3, volume = pdx^3)."""
 
     def __init__(self, gres, gdx, bound_min, rb_d, px, pdx, rho=1000.0, mu=1.0, dt=1.0 / 300.0, device="cuda",
-                 precision=None, jacobi=False):
+                 precision=None, jacobi=False, motion=None):
         """jacobi=True: the build's opt-in Jacobi preconditioning for the viscosity and pressure solves (NOT the reference's
-        iterations -- same stopping rules, a fraction of the CG iterations; single-GPU class only)"""
+        iterations -- same stopping rules, a fraction of the CG iterations; single-GPU class only)
+        motion: {body index: mfs.motion.Motion} -- those bodies move; `rb_d` is updated in place every step and the solid
+        level set and velocity are re-evaluated at the new pose (`_move_solids`).  None: solids are static scene data."""
         dev = torch.device(device)
         g = tuple(int(v) for v in gres)
         self.GRES, self.GDX, self.PDX, self.RHO, self.MU, self.DT = g, float(gdx), float(pdx), float(rho), float(mu), float(dt)
@@ -79,6 +82,7 @@ class NotebookSimulation:
                                  phi=torch.zeros(g, dtype=torch.float64, device=dev))
         self.fluid_volume = NS(resolution=dres, bound_size=bsz, bound_min=bmin, cell_size=dcs,
                                vol=torch.zeros(dres, dtype=torch.float64, device=dev))
+        self.kinematics = BodyKinematics(rb_d, motion, 3) if motion else None
         self._precision = precision
         self._jacobi = bool(jacobi)
         self._make_solvers()
@@ -96,6 +100,15 @@ class NotebookSimulation:
             self.PressureSolver._engine.set_jacobi(True)
             self.ViscositySolver._engine.set_jacobi(True)
             self.DensitySolver._engine.set_jacobi(True)      # (the pressure engine with the density operator's -z tap)
+
+    def _move_solids(self, t0, dt, tick, t):
+        """bodies to their pose at t0 + dt, particles out of them, solid level set and surface velocity at the new pose"""
+        sl = self.solid_levelset
+        self.kinematics.advance(t0, dt)
+        sdf.project(self.rb_d, self.particle.x)
+        t = tick("advect+project", t)
+        sdf.evaluate_grid(self.rb_d, sl.phi, sl.v, sl.bound_min, sl.cell_size, sl.bias, rb_w=self.kinematics.rb_w)
+        return tick("solid", t)
 
     def _solve_grid(self, dt, tick, t):
         """the two hot-path solves of the loop body (ipynb:4623, 4648) on the grid velocities, in place"""
@@ -121,10 +134,16 @@ class NotebookSimulation:
         vmax = torch.sqrt((p.v ** 2).sum(dim=-1)).max().item() if p.num_particles else 0.0
         cfl_dt = self.GDX / max(1e-10, vmax)
         dt = min(self.DT, cfl_dt, duration_left)
+        t0 = self.current_time
+        if self.kinematics is not None:                                     # a body crosses at most one cell per step
+            dt = min(dt, self.GDX / max(1e-10, self.kinematics.max_surface_speed(t0)))
         self.current_time += dt
         p.x += p.v * dt
-        sdf.project(self.rb_d, p.x)
-        t = tick("advect+project", t)
+        if self.kinematics is not None:
+            t = self._move_solids(t0, dt, tick, t)
+        else:
+            sdf.project(self.rb_d, p.x)
+            t = tick("advect+project", t)
         K.compute_fluid_levelset(p, fl, self.GDX)
         K.compute_fluid_volume(p, fv, p.vol)
         t = tick("levelset+volume", t)
@@ -162,7 +181,10 @@ class SlabNotebookSimulation(NotebookSimulation):
     Amdahl: with the fraction f of a one-GPU step in the three loops the step takes (1 - f) + f / N; sharding the
     particles (migration between slabs) is the next step.  `step` is collective."""
 
-    def __init__(self, *args, dist, group=None, transport="auto", **kw):
+    def __init__(self, *args, dist, group=None, transport="auto", motion=None, **kw):
+        if motion:
+            raise ValueError("motion: the slab / sharded time steps treat solids as static scene data; moving bodies need "
+                             "the single-GPU NotebookSimulation")
         self.dist, self.group, self._transport = dist, group, transport
         super().__init__(*args, **kw)      # (jacobi=True: honoured by the window slab loops; the collective loops drop it with a warning)
 
@@ -232,8 +254,8 @@ class ShardedNotebookSimulation(SlabNotebookSimulation):
 
     GHOST, REACH = 4, 3        # cells: ghost band maintained around the range; scatter reach (5^3 level-set stencil + slack)
 
-    def __init__(self, *args, dist, group=None, transport="auto", **kw):
-        super().__init__(*args, dist=dist, group=group, transport=transport, **kw)
+    def __init__(self, *args, dist, group=None, transport="auto", motion=None, **kw):
+        super().__init__(*args, dist=dist, group=group, transport=transport, motion=motion, **kw)
         from mfs.dist import SlabBands
         self.bands = SlabBands(dist, group, self.GRES[0], device=self.device)
         p = self.particle

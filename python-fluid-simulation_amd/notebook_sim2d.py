@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 import notebook_kernels2d as K
+from mfs.motion import BodyKinematics
 from solver import sdf2D as sdf
 from solver.CGSolverBuffer import CGSolverBuffer
 from solver.DensityCGSolver2D import DensityCGSolver2D
@@ -36,10 +37,12 @@ def grid_positions(res, bound_min, cell_size, bias, device):
 
 class NotebookSimulation2D:
     """gres, gdx: cell grid (Nx, Ny) and spacing; bound_min: float32 pair; rb_d: packed rigid bodies (solver.sdf2D);
-    px: (P,2) float64 particle positions; pdx: particle spacing (mass = rho * pdx^2, volume = pdx^2)."""
+    px: (P,2) float64 particle positions; pdx: particle spacing (mass = rho * pdx^2, volume = pdx^2);
+    motion: {body index: mfs.motion.Motion} -- those bodies move: `rb_d` is updated in place every step and the solid level
+    set and velocity are re-evaluated at the new pose.  None: solids are static scene data."""
 
     def __init__(self, gres, gdx, bound_min, rb_d, px, pdx, rho=1000.0, mu=1.0, dt=1.0 / 300.0, device="cuda",
-                 precision=None):
+                 precision=None, motion=None):
         dev = torch.device(device)
         g = tuple(int(v) for v in gres)
         if len(g) != 2:
@@ -75,6 +78,7 @@ class NotebookSimulation2D:
                                  phi=torch.zeros(g, dtype=torch.float64, device=dev))
         self.fluid_volume = NS(resolution=dres, bound_size=bsz, bound_min=bmin, cell_size=dcs,
                                vol=torch.zeros(dres, dtype=torch.float64, device=dev))
+        self.kinematics = BodyKinematics(rb_d, motion, 2) if motion else None
         self._precision = precision
         self.CGBuf = CGSolverBuffer(g, precision=precision, device=dev)
         self.PressureSolver = PressureCGSolver2D(self.CGBuf, g, self.BOUND_SIZE)
@@ -97,10 +101,18 @@ class NotebookSimulation2D:
         vmax = torch.sqrt((p.v ** 2).sum(dim=-1)).max().item() if p.num_particles else 0.0
         cfl_dt = self.GDX / max(1e-10, vmax)
         dt = min(self.DT, cfl_dt, duration_left)
+        t0 = self.current_time
+        if self.kinematics is not None:                                     # a body crosses at most one cell per step
+            dt = min(dt, self.GDX / max(1e-10, self.kinematics.max_surface_speed(t0)))
         self.current_time += dt
         p.x += p.v * dt
+        if self.kinematics is not None:                                     # bodies to their pose at t0 + dt
+            self.kinematics.advance(t0, dt)
         sdf.project(self.rb_d, p.x)
         t = tick("advect+project", t)
+        if self.kinematics is not None:                                     # solid level set and surface velocity there
+            sdf.evaluate_grid(self.rb_d, sl.phi, sl.v, sl.bound_min, sl.cell_size, sl.bias, rb_w=self.kinematics.rb_w)
+            t = tick("solid", t)
         K.compute_fluid_levelset(p, fl, self.GDX)
         K.compute_fluid_volume(p, fv, p.vol)
         t = tick("levelset+volume", t)

@@ -91,6 +91,28 @@ def evaluate(rb_d, sd, vel, position):
                                       T.code(sd), T.ptr(vel), T.code(vel), T.stream()), "mfs_sdf_evaluate2d")
 
 
+def evaluate_grid(rb_d, sd, vel, bound_min, cell_size, bias, rb_w=None):
+    """`evaluate` on the nodes of a regular grid, for bodies that move (no reference counterpart): sd has the grid's shape,
+    vel that shape + (2,); the position of index i along an axis is `grid_positions`' bound_min(f32) + (f32 i + f32 bias)
+    * cell_size, made in the kernel, and every element of vel is written -- no position array, no zeroing pass.
+    rb_w: float64 (n,) angular velocities in rad/s; the winning body's velocity is then v + w x (pos - centre)."""
+    rb_d = _bodies(rb_d)
+    sd, vel = T.dev(sd, "sd"), T.dev(vel, "vel")
+    if sd.dim() != 2 or tuple(vel.shape) != tuple(sd.shape) + (2,):
+        raise ValueError(f"sd / vel: expected shapes (n0, ..) and (n0, .., 2) on a 2D grid, got {tuple(sd.shape)}, {tuple(vel.shape)}")
+    n = int(rb_d.shape[0])
+    if rb_w is not None:
+        rb_w = T.dev(rb_w, "rb_w", (n,))
+        if rb_w.dtype != torch.float64:
+            raise TypeError("rb_w: expected float64")
+    lib = _lib.load()
+    f = lambda a: _lib.f64x(T.as_f64_list(a, 2))  # noqa: E731
+    _lib.check(lib.mfs_sdf_evaluate_grid2d(T.ptr(rb_d), n, None if rb_w is None or n == 0 else T.ptr(rb_w),
+                                           _lib.i64x(tuple(int(v) for v in sd.shape)), f(bound_min), f(bias), f(cell_size),
+                                           T.ptr(sd), T.code(sd), T.ptr(vel), T.code(vel), T.stream()),
+               "mfs_sdf_evaluate_grid2d")
+
+
 def project(rb_d, position):
     """In place: every body in turn moves the points it owns to its surface / into itself
     (reference :198-205 -> kernel :171-183)."""

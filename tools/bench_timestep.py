@@ -3,7 +3,9 @@ scene scaled to an N^3 grid -- flipped container box, four slanted obstacle plat
 block of (N/2)^3 cells at 8 particles per cell -- stepped with notebook_sim.NotebookSimulation; per-stage
 wall-clock (synchronised), CG iteration counts.   usage: python tools/bench_timestep.py [N] [steps] [mu]
 Under `python -m torch.distributed.run --nproc-per-node R ...` (one rank per GPU, RCCL) the two hot-path solves run
-slab-decomposed (notebook_sim.SlabNotebookSimulation); MFS_BENCH_SHARED_GPU=1 = rehearsal with all ranks on cuda:0 / gloo."""
+slab-decomposed (notebook_sim.SlabNotebookSimulation); MFS_BENCH_SHARED_GPU=1 = rehearsal with all ranks on cuda:0 / gloo.
+MFS_TIMESTEP_MOTION=1 (single GPU): plate p1 moves at (0.2, 0, 0) and turns at 1 rad/s about z -- the step then re-evaluates
+the solid level set every step (stage "solid")."""
 import json, os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(REPO, "python-fluid-simulation_amd"), REPO]
@@ -39,8 +41,12 @@ rng = np.random.default_rng(0)
 t0 = time.perf_counter()
 px = NSIM.add_box([0.0, 0.7, 0.0], [0.5, 0.5, 0.5], gdx / 2, rng)
 if dist is None:
+    motion = None
+    if os.environ.get("MFS_TIMESTEP_MOTION", "0") == "1":
+        from mfs.motion import Motion
+        motion = {rb_map["p1"]: Motion(velocity=[0.2, 0.0, 0.0], omega=[0.0, 0.0, 1.0])}
     sim = NSIM.NotebookSimulation((N, N, N), gdx, bmin, rb_d, px, gdx / 2, mu=mu, device=dev, precision=os.environ.get("MFS_PRECISION"),
-                                  jacobi=os.environ.get("MFS_TIMESTEP_JACOBI", "0") == "1")
+                                  jacobi=os.environ.get("MFS_TIMESTEP_JACOBI", "0") == "1", motion=motion)
 else:
     # MFS_TIMESTEP_PARTICLES=replicated: the round-1 form (every rank holds all particles, whole-grid broadcasts)
     cls = NSIM.SlabNotebookSimulation if os.environ.get("MFS_TIMESTEP_PARTICLES") == "replicated" else NSIM.ShardedNotebookSimulation
