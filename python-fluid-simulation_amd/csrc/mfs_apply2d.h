@@ -71,10 +71,4 @@ k_apply2d(Grid2 g, const void* v, void* out, int dt, const void* wx, const void*
   }
 }
 
-static inline int check_gres2(const int64_t gres[2]) {
-  MFS_REQUIRE(gres != nullptr, "gres is null");
-  MFS_REQUIRE(gres[0] >= 1 && gres[1] >= 1 && gres[0] <= 65536 && gres[1] <= 65536, "grid resolution out of range");
-  return MFS_OK;
-}
-
 }  // namespace mfs

@@ -1426,4 +1426,32 @@ static inline int64_t core_history(CgCore& c, double* out_host, int64_t cap, hip
   return cnt;
 }
 
+// The plain device-resident loop of an engine with no loop form of its own (the 2D engines): q = A x, r = d = b - q, then
+// batches of check_every x {q = A d, x / r update, d update} with one poll (the only host sync) between batches.
+// `apply(v, out, use_done)` is the engine's stencil launch.  Returns MFS_NOT_CONVERGED after max_iter iterations.
+template <typename Apply>
+static inline int core_solve(CgCore& c, double tol, bool zero_x, int64_t max_iter, int64_t check_every, hipStream_t st,
+                             int64_t* iters_host, Apply apply) {
+  int e;
+  if ((e = core_begin_pre(c, tol, zero_x, st))) return e;
+  if ((e = apply(c.x, c.q, false))) return e;
+  if ((e = core_begin_post(c, st))) return e;
+  if ((e = core_begin_finish(c, st))) return e;
+  int64_t enq = 0, iters = 0;
+  int done = 0;
+  if ((e = core_poll(c, st, &iters, &done, nullptr, nullptr, nullptr))) return e;
+  while (!done && enq < max_iter) {
+    const int64_t n = std::min(check_every, max_iter - enq);
+    for (int64_t i = 0; i < n; ++i) {
+      if ((e = apply(c.d, c.q, true))) return e;
+      if ((e = core_update_xr(c, true, st))) return e;
+      if ((e = core_update_d(c, true, st))) return e;
+    }
+    enq += n;
+    if ((e = core_poll(c, st, &iters, &done, nullptr, nullptr, nullptr))) return e;
+  }
+  if (iters_host) *iters_host = iters;
+  return done ? MFS_OK : MFS_NOT_CONVERGED;
+}
+
 }  // namespace mfs

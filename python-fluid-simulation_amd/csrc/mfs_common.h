@@ -125,6 +125,13 @@ template <> struct VecOf<double> { static constexpr int N = 2; };
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// grid resolution of a 2D entry point (the 3D files keep their own range checks)
+static inline int check_gres2(const int64_t gres[2]) {
+  MFS_REQUIRE(gres != nullptr, "gres is null");
+  MFS_REQUIRE(gres[0] >= 1 && gres[1] >= 1 && gres[0] <= 65536 && gres[1] <= 65536, "grid resolution out of range");
+  return MFS_OK;
+}
+
 // integer knob from the environment (tuning / test hooks only)
 static inline int env_int(const char* name, int defv) {
   const char* s = getenv(name);

@@ -203,26 +203,8 @@ int mfs_pcg2d_solve(mfs_pcg2d* h, double tol, int64_t max_iter, int64_t check_ev
   MFS_REQUIRE(h && h->c.x && h->lphi, "engine not bound / set up");
   MFS_REQUIRE(max_iter >= 0 && check_every >= 1, "max_iter / check_every");
   hipStream_t st = (hipStream_t)stream;
-  int e;
-  if ((e = core_begin_pre(h->c, tol, true, st))) return e;
-  if ((e = apply2d(h, h->c.x, h->c.q, false, st))) return e;
-  if ((e = core_begin_post(h->c, st))) return e;
-  if ((e = core_begin_finish(h->c, st))) return e;
-  int64_t enq = 0, iters = 0;
-  int done = 0;
-  if ((e = core_poll(h->c, st, &iters, &done, nullptr, nullptr, nullptr))) return e;
-  while (!done && enq < max_iter) {
-    const int64_t n = std::min(check_every, max_iter - enq);
-    for (int64_t i = 0; i < n; ++i) {
-      if ((e = apply2d(h, h->c.d, h->c.q, true, st))) return e;
-      if ((e = core_update_xr(h->c, true, st))) return e;
-      if ((e = core_update_d(h->c, true, st))) return e;
-    }
-    enq += n;
-    if ((e = core_poll(h->c, st, &iters, &done, nullptr, nullptr, nullptr))) return e;
-  }
-  if (iters_host) *iters_host = iters;
-  return done ? MFS_OK : MFS_NOT_CONVERGED;
+  return core_solve(h->c, tol, true, max_iter, check_every, st, iters_host,
+                    [=](const void* v, void* out, bool use_done) { return apply2d(h, v, out, use_done, st); });
 }
 
 int64_t mfs_pcg2d_history(mfs_pcg2d* h, double* out_host, int64_t cap, mfs_stream stream) {

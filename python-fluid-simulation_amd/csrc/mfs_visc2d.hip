@@ -277,12 +277,6 @@ struct mfs_vcg2d {
   int grid;
 };
 
-static int check_gres_v2(const int64_t gres[2]) {
-  MFS_REQUIRE(gres != nullptr, "gres is null");
-  MFS_REQUIRE(gres[0] >= 1 && gres[1] >= 1 && gres[0] <= 65536 && gres[1] <= 65536, "grid resolution out of range");
-  return MFS_OK;
-}
-
 static size_t vcg2d_tables_bytes(const int64_t gres[2]) {
   const size_t nc = (size_t)(gres[0] + 1) * (size_t)(gres[1] + 1);
   return 4 * align_up(nc * 8, 256) + align_up(nc * 4, 256);
@@ -306,7 +300,7 @@ extern "C" {
 int mfs_visc_rhs2d(const int64_t gres[2], double scale, double mu, const void* vx, const void* vy, int v_dt,
                    const void* sphi, int sphi_dt, const void* vol, int vol_dt, void* b_x, void* b_y, int b_dt,
                    mfs_stream stream) {
-  if (int e = check_gres_v2(gres)) return e;
+  if (int e = check_gres2(gres)) return e;
   MFS_REQUIRE(vx && vy && sphi && vol && b_x && b_y, "null array");
   MFS_REQUIRE(b_x != b_y && b_x != vx && b_x != vy && b_y != vx && b_y != vy, "aliased array");
   MFS_REQUIRE(dtype_ok(v_dt) && dtype_ok(sphi_dt) && dtype_ok(vol_dt) && dtype_ok(b_dt), "dtype");
@@ -321,7 +315,7 @@ int mfs_visc_rhs2d(const int64_t gres[2], double scale, double mu, const void* v
 int mfs_visc_apply2d(const int64_t gres[2], double scale, double mu, const void* vx, const void* vy, int v_dt,
                      void* out_x, void* out_y, int out_dt, const void* sphi, int sphi_dt, const void* vol, int vol_dt,
                      mfs_stream stream) {
-  if (int e = check_gres_v2(gres)) return e;
+  if (int e = check_gres2(gres)) return e;
   MFS_REQUIRE(vx && vy && out_x && out_y && sphi && vol, "null array");
   MFS_REQUIRE(out_x != out_y && out_x != vx && out_x != vy && out_y != vx && out_y != vy, "aliased array");
   MFS_REQUIRE(dtype_ok(v_dt) && dtype_ok(out_dt) && dtype_ok(sphi_dt) && dtype_ok(vol_dt), "dtype");
@@ -335,7 +329,7 @@ int mfs_visc_apply2d(const int64_t gres[2], double scale, double mu, const void*
 
 int mfs_visc_writeback2d(const int64_t gres[2], void* vx, void* vy, int v_dt, const void* out_x, const void* out_y,
                          int out_dt, const void* sphi, int sphi_dt, mfs_stream stream) {
-  if (int e = check_gres_v2(gres)) return e;
+  if (int e = check_gres2(gres)) return e;
   MFS_REQUIRE(vx && vy && out_x && out_y && sphi, "null array");
   MFS_REQUIRE(vx != vy && vx != out_x && vx != out_y && vy != out_x && vy != out_y, "aliased array");
   MFS_REQUIRE(dtype_ok(v_dt) && dtype_ok(out_dt) && dtype_ok(sphi_dt), "dtype");
@@ -359,7 +353,7 @@ size_t mfs_vcg2d_workspace_bytes(const int64_t gres[2], int dt) {
 int mfs_vcg2d_create(mfs_vcg2d** out, const int64_t gres[2], int dt, void* workspace, size_t workspace_bytes,
                      mfs_stream stream) {
   MFS_REQUIRE(out && workspace, "null argument");
-  if (int e = check_gres_v2(gres)) return e;
+  if (int e = check_gres2(gres)) return e;
   MFS_REQUIRE(dtype_ok(dt), "dtype");
   MFS_REQUIRE(((uintptr_t)workspace % 256) == 0, "workspace must be 256-byte aligned");
   MFS_REQUIRE(workspace_bytes >= mfs_vcg2d_workspace_bytes(gres, dt), "workspace too small");
@@ -432,26 +426,8 @@ int mfs_vcg2d_solve(mfs_vcg2d* h, double tol, int64_t max_iter, int64_t check_ev
   MFS_REQUIRE(h && h->c.x && h->set_up, "engine not bound / set up");
   MFS_REQUIRE(max_iter >= 0 && check_every >= 1, "max_iter / check_every");
   hipStream_t st = (hipStream_t)stream;
-  int e;
-  if ((e = core_begin_pre(h->c, tol, false, st))) return e;
-  if ((e = vcg2d_apply(h, h->c.x, h->c.q, false, st))) return e;
-  if ((e = core_begin_post(h->c, st))) return e;
-  if ((e = core_begin_finish(h->c, st))) return e;
-  int64_t enq = 0, iters = 0;
-  int done = 0;
-  if ((e = core_poll(h->c, st, &iters, &done, nullptr, nullptr, nullptr))) return e;
-  while (!done && enq < max_iter) {
-    const int64_t n = std::min(check_every, max_iter - enq);
-    for (int64_t i = 0; i < n; ++i) {
-      if ((e = vcg2d_apply(h, h->c.d, h->c.q, true, st))) return e;
-      if ((e = core_update_xr(h->c, true, st))) return e;
-      if ((e = core_update_d(h->c, true, st))) return e;
-    }
-    enq += n;
-    if ((e = core_poll(h->c, st, &iters, &done, nullptr, nullptr, nullptr))) return e;
-  }
-  if (iters_host) *iters_host = iters;
-  return done ? MFS_OK : MFS_NOT_CONVERGED;
+  return core_solve(h->c, tol, false, max_iter, check_every, st, iters_host,
+                    [=](const void* v, void* out, bool use_done) { return vcg2d_apply(h, v, out, use_done, st); });
 }
 
 int64_t mfs_vcg2d_history(mfs_vcg2d* h, double* out_host, int64_t cap, mfs_stream stream) {

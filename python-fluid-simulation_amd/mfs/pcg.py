@@ -1,46 +1,15 @@
-"""Python owner of one `mfs_pcg3d` engine handle (include/mfs.h): allocates the
-device workspace with torch, keeps it alive, and exposes the C entry points."""
+"""Python owners of the pressure engine handles `mfs_pcg3d` and `mfs_pcg2d` (include/mfs.h); what they share with
+the viscosity engines is in engine.py."""
 from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
-import torch
-
 from . import _lib, tensors as T
+from .engine import CgEngine
 
 
-class PcgEngine:
-    def __init__(self, gres, dtype, device=None):
-        self.lib = _lib.load()
-        self.gres = T.as_gres(gres)
-        if len(self.gres) != 3:
-            raise ValueError("PcgEngine is 3D")
-        self.dtype = T.state_dtype(dtype)
-        self.code = _lib.MFS_F32 if self.dtype == torch.float32 else _lib.MFS_F64
-        self.device = torch.device("cuda" if device is None else device)
-        g = _lib.i64x(self.gres)
-        nbytes = int(self.lib.mfs_pcg3d_workspace_bytes(g, self.code))
-        if nbytes <= 0:
-            raise _lib.MfsError("mfs_pcg3d_workspace_bytes returned 0")
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.mfs_pcg3d_create(C.byref(h), g, self.code, T.ptr(self.workspace), nbytes, T.stream()),
-                       "mfs_pcg3d_create")
-        self.h = h
-        # the engine's scalar block is the first 128 bytes of the workspace
-        self.scalars = self.workspace[: _lib.NSCALARS * 8].view(torch.float64)
-        assert self.scalars.data_ptr() == self.lib.mfs_pcg3d_scalars(self.h)
-        self._bound = None
-
-    def __del__(self):
-        h, self.h = getattr(self, "h", None), None
-        if h:
-            try:
-                self.lib.mfs_pcg3d_destroy(h)
-            except Exception:
-                pass
+class PcgEngine(CgEngine):
+    PREFIX, RANK = "mfs_pcg3d", 3
 
     def tune(self, variant=2, xchunk=0, blocks_per_cu=2, nontemporal=-1):
         _lib.check(self.lib.mfs_pcg3d_tune(self.h, int(variant), int(xchunk), int(blocks_per_cu), int(nontemporal)),
@@ -62,8 +31,7 @@ class PcgEngine:
         _lib.check(self.lib.mfs_pcg3d_set_sparse(self.h, int(bool(on))), "mfs_pcg3d_set_sparse")
 
     def sparse_info(self):
-        import ctypes
-        out = (ctypes.c_int64 * 4)()
+        out = _lib.i64x([0] * 4)
         _lib.check(self.lib.mfs_pcg3d_sparse_info(self.h, T.stream(), out), "mfs_pcg3d_sparse_info")
         return dict(live_chunks=int(out[0]), chunks=int(out[1]), listed_pairs=int(out[2]), pairs=int(out[3]))
 
@@ -109,14 +77,6 @@ class PcgEngine:
         _lib.check(self.lib.mfs_pcg3d_setup_density(self.h, T.ptr(lphi), T.code(lphi), T.ptr(wx), T.ptr(wy), T.ptr(wz),
                                                     T.code(wx), T.stream()), "mfs_pcg3d_setup_density")
 
-    def bind(self, b, x, d, r, q):
-        ts = [T.dev(a, n, self.gres) for a, n in ((b, "b"), (x, "x"), (d, "d"), (r, "r"), (q, "q"))]
-        for t in ts:
-            if t.dtype != self.dtype:
-                raise TypeError(f"CG vectors must be {self.dtype}, got {t.dtype}")
-        _lib.check(self.lib.mfs_pcg3d_bind(self.h, *[T.ptr(t) for t in ts]), "mfs_pcg3d_bind")
-        self._bound = ts          # keep the tensors alive while the engine points at them
-
     # -- the hot kernel on its own ---------------------------------------------
     def apply(self, v, out, x_begin=None, x_end=None):
         v = T.dev(v, "v", self.gres)
@@ -141,40 +101,6 @@ class PcgEngine:
 
     def native_finish(self):
         _lib.check(self.lib.mfs_pcg3d_native_finish(self.h, T.stream()), "mfs_pcg3d_native_finish")
-
-    def poll(self):
-        it, done = C.c_int64(), C.c_int()
-        delta, alpha, beta = C.c_double(), C.c_double(), C.c_double()
-        _lib.check(self.lib.mfs_pcg3d_poll(self.h, T.stream(), C.byref(it), C.byref(done), C.byref(delta),
-                                           C.byref(alpha), C.byref(beta)), "mfs_pcg3d_poll")
-        return dict(iterations=it.value, done=bool(done.value), delta=delta.value, alpha=alpha.value,
-                    beta=beta.value)
-
-    def poll_raw(self):
-        """the scalar block as it stands, WITHOUT raising on the loop's error word (diagnostics after a failed solve)"""
-        s = self.scalars.cpu()
-        return dict(iterations=int(s[_lib.S_ITERS]), done=bool(s[_lib.S_DONE] != 0), delta=float(s[_lib.S_LASTRR]),
-                    err=int(s[_lib.S_ERR]))
-
-    def solve(self, tol, max_iter, check_every=32):
-        it = C.c_int64()
-        st = _lib.check(self.lib.mfs_pcg3d_solve(self.h, float(tol), int(max_iter), int(check_every), T.stream(),
-                                                 C.byref(it)), "mfs_pcg3d_solve")
-        return st == _lib.MFS_OK, it.value
-
-    def history(self):
-        cap = int(self.lib.mfs_pcg3d_history_capacity())
-        buf = np.empty(cap, dtype=np.float64)
-        n = self.lib.mfs_pcg3d_history(self.h, buf.ctypes.data_as(C.POINTER(C.c_double)), cap, T.stream())
-        _lib.check(int(n), "mfs_pcg3d_history")
-        return buf[: int(n)].copy()
-
-    def history_truncated(self):
-        """True when the solve ran past the history buffer (capacity mfs_pcg3d_history_capacity() doubles = 8 191 iterations):
-        history() then holds the LEADING entries only -- `iterations`, `delta`, alpha and beta come from the engine's scalar
-        block (poll()), never from the history, and stay exact"""
-        cap = int(self.lib.mfs_pcg3d_history_capacity())
-        return 2 * int(self.poll_raw()["iterations"]) + 1 > cap
 
     # -- single phases (multi-GPU driver) ------------------------------------------
     def phase_apply(self, xb, xe, first):
@@ -235,3 +161,31 @@ class PcgEngine:
         st = _lib.check(self.lib.mfs_pcg3d_slab_solve(self.h, float(tol), int(max_iter), int(check_every), T.stream(),
                                                       C.byref(it)), "mfs_pcg3d_slab_solve")
         return st == _lib.MFS_OK, it.value
+
+
+class Pcg2dEngine(CgEngine):
+    """the 2D pressure engine; PressureCGSolver2D and DensityCGSolver2D run their loops on it"""
+    PREFIX, RANK = "mfs_pcg2d", 2
+
+    def _operator(self, lphi, wx, wy):
+        g = self.gres
+        lphi = T.dev(lphi, "lphi", g)
+        wx, wy = T.dev(wx, "wx", T.face_shape(g, 0)), T.dev(wy, "wy", T.face_shape(g, 1))
+        if wx.dtype != wy.dtype:
+            raise TypeError("wx, wy must share a dtype")
+        self._operands = (lphi, wx, wy)     # read by every later apply / solve, not copied: keep them alive
+        return T.ptr(lphi), T.code(lphi), T.ptr(wx), T.ptr(wy), T.code(wx)
+
+    def setup(self, lphi, wx, wy):
+        _lib.check(self.lib.mfs_pcg2d_setup(self.h, *self._operator(lphi, wx, wy)), "mfs_pcg2d_setup")
+
+    def setup_density(self, lphi, wx, wy):
+        """the density solver's operator (solver/DensityCGSolver2D.py:85-139) instead of the pressure one"""
+        _lib.check(self.lib.mfs_pcg2d_setup_density(self.h, *self._operator(lphi, wx, wy)), "mfs_pcg2d_setup_density")
+
+    def apply(self, v, out):
+        """out = A v in the mode the last setup chose (boundary cells of `out` untouched)"""
+        v, out = self._vector(v, "v"), self._vector(out, "out")
+        if v.dtype != self.dtype or out.dtype != self.dtype:
+            raise TypeError(f"apply operands must be {self.dtype}")
+        _lib.check(self.lib.mfs_pcg2d_apply(self.h, T.ptr(v), T.ptr(out), T.stream()), "mfs_pcg2d_apply")

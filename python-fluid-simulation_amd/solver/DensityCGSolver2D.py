@@ -9,12 +9,11 @@ What the 2D reference does differently from its 3D twin, kept: the splat writes 
 `fix_volume` from `lvol`), the loop does NOT raise when `max_iter` runs out, and the y gather samples at the positions
 the x gather has already moved.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from mfs import _lib, tensors as T
+from mfs.pcg import Pcg2dEngine
 from .SolidFraction2D import compute_solid_frac, edge_in_fraction  # noqa: F401  (reference line 6)
 
 
@@ -157,41 +156,20 @@ class DensityCGSolver2D:
         self.check_every = int(check_every)
         self.iterations = 0
         self.converged = False
-        self._lib = _lib.load()
-        code = _lib.MFS_F32 if dt == torch.float32 else _lib.MFS_F64
-        gi = _lib.i64x(self._g)
-        nbytes = int(self._lib.mfs_pcg2d_workspace_bytes(gi, code))
-        self._ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(self._lib.mfs_pcg2d_create(C.byref(h), gi, code, T.ptr(self._ws), nbytes, T.stream()),
-                       "mfs_pcg2d_create")
-        self._h = h
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                self._lib.mfs_pcg2d_destroy(h)
-            except Exception:
-                pass
+        self._engine = Pcg2dEngine(self._g, dt, device)
 
     @property
     def history(self):
-        cap = int(self._lib.mfs_pcg3d_history_capacity())
-        buf = np.empty(cap, dtype=np.float64)
-        n = self._lib.mfs_pcg2d_history(self._h, buf.ctypes.data_as(C.POINTER(C.c_double)), cap, T.stream())
-        _lib.check(int(n), "mfs_pcg2d_history")
-        return buf[: int(n)].copy()
+        return self._engine.history()
 
     @property
     def history_truncated(self):
         """True if the last solve ran past the history buffer (8 191 iterations); `iterations` / `delta` stay exact"""
-        return 2 * int(self.iterations) + 1 > int(self._lib.mfs_pcg3d_history_capacity())
+        return self._engine.history_truncated()
 
     def solve(self, rho0, dt, px, pm, pvol, vx, vy, sphi, sv, lphi, lvol, wx=None, wy=None, tol=1e-3):
         """`vx`, `vy`, `sv` are accepted and never read, as in the reference; `px` is moved in place, in its dtype."""
-        g, lib = self._g, self._lib
+        g, eng = self._g, self._engine
         if wx is None or wy is None:
             compute_solid_frac(self.gres, sphi, self.wx, self.wy)
             wx, wy = self.wx, self.wy
@@ -202,22 +180,11 @@ class DensityCGSolver2D:
             initialize_density(self.bound_min, self.cell_size, g, px, pm, pvol, self.m, self.vol, sphi, lphi)
             fix_volume(self.cell_size, g, lvol, self.vol, sphi, lphi, wx, wy)
             initialize_solver(rho0, dt, g, self.cell_size, self.m, self.vol, lphi, wx, wy, self.buf.b)
-            lphi_t = T.dev(lphi, "lphi", g)
-            wx_t, wy_t = _faces(g, wx, wy)
-            _lib.check(lib.mfs_pcg2d_setup_density(self._h, T.ptr(lphi_t), T.code(lphi_t), T.ptr(wx_t), T.ptr(wy_t),
-                                                   T.code(wx_t)), "mfs_pcg2d_setup_density")
-            vecs = [T.dev(a, n, g) for a, n in ((self.buf.b, "b"), (self.x, "x"), (self.buf.d, "d"),
-                                                (self.buf.r, "r"), (self.buf.q, "q"))]
-            _lib.check(lib.mfs_pcg2d_bind(self._h, *[T.ptr(t) for t in vecs]), "mfs_pcg2d_bind")
-            it = C.c_int64()
-            st = _lib.check(lib.mfs_pcg2d_solve(self._h, float(tol), int(self.max_iter), self.check_every, T.stream(),
-                                                C.byref(it)), "mfs_pcg2d_solve")
-            self.iterations, self.converged = it.value, st == _lib.MFS_OK
-            done = C.c_int()
-            d_, a_, b_ = C.c_double(), C.c_double(), C.c_double()
-            _lib.check(lib.mfs_pcg2d_poll(self._h, T.stream(), C.byref(it), C.byref(done), C.byref(d_), C.byref(a_),
-                                          C.byref(b_)), "mfs_pcg2d_poll")
-            self.alpha, self.beta, self.delta = a_.value, b_.value, d_.value
+            eng.setup_density(lphi, wx, wy)
+            eng.bind(self.buf.b, self.x, self.buf.d, self.buf.r, self.buf.q)
+            self.converged, self.iterations = eng.solve(tol, self.max_iter, self.check_every)
+            p = eng.poll()
+            self.alpha, self.beta, self.delta = p["alpha"], p["beta"], p["delta"]
             # self.x : -pressure * dt / rho / dx^2
             compute_displacement(g, dt, self.cell_size, self.dx, self.dy, self.x, lphi)
             apply_displacement(px, self.dx, self.bound_min, self.cell_size, self.bias_x, 0)

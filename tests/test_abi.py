@@ -51,6 +51,20 @@ def test_every_declared_symbol_is_exported(lib):
     assert set(_lib.SIGNATURES) == set(decl)
 
 
+def test_engine_classes_form_only_declared_names():
+    """mfs/engine.py forms the shared entry points' names from a class's C prefix: a typo there would otherwise show
+    only at the first call on a GPU"""
+    from mfs import _lib
+    from mfs.pcg import Pcg2dEngine, PcgEngine
+    from mfs.vcg import Vcg2dEngine, VcgEngine
+    for cls, prefix, n in ((PcgEngine, "mfs_pcg3d", 8), (VcgEngine, "mfs_vcg3d", 11), (Pcg2dEngine, "mfs_pcg2d", 7),
+                           (Vcg2dEngine, "mfs_vcg2d", 10)):
+        names = cls.c_names()
+        assert len(set(names)) == n and all(name.startswith(prefix + "_") for name in names), (cls, names)
+        missing = [name for name in names if name not in _lib.SIGNATURES]
+        assert not missing, (cls.__name__, missing)
+
+
 def test_abi_version_and_error_text(lib):
     from mfs import _lib
     assert lib.mfs_abi_version() == _lib.ABI_VERSION
