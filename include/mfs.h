@@ -719,6 +719,41 @@ int mfs_grid_boundary_condition2d(const int64_t gres[2], const void* gvx, const 
                                   const void* sphi, int sphi_dt, const void* sv, int sv_dt, double dx,
                                   void* dvx, void* dvy, int dv_dt, mfs_stream stream);
 
+/* ------------------------------------------------------------------------- */
+/* Surface extraction (csrc/mfs_surface.hip; DESIGN.md "Surface extraction")  */
+/* ------------------------------------------------------------------------- */
+/* What the notebook does with a CPU marching-cubes routine after scene set-up and after the run, on the device: an
+ * indexed, welded, consistently oriented triangle mesh of {phi < level} by marching tetrahedra over the six Kuhn
+ * tetrahedra of every lattice cube.  No atomics: the output is a function of the field alone.
+ * phi: shape[0] x shape[1] x shape[2] in C order, every extent >= 2; a node is inside iff phi < level (NaN never is).
+ * closed != 0: the lattice is the array plus one virtual layer of samples of value `outside` (> level) on every side;
+ * nothing is copied.  The lattice may hold at most 2^31 - 1025 nodes.
+ * Two passes.  _count classifies and leaves the totals in the first 16 bytes of `workspace` (DEVICE memory, 256-byte
+ * aligned): int64 vertices, int64 triangles.  The caller reads them, allocates, and calls _fill with the SAME shape, phi,
+ * level, closed, outside and workspace.  _fill reads the totals back itself (it drains `stream`), returns MFS_E_INVALID
+ * without a launch when a capacity is smaller than its total or a total does not fit int32 (3 x triangles included),
+ * and never writes past a capacity.  Totals of zero: MFS_OK, nothing written, the array pointers may be null.
+ * vertices: cap_vertices x 3 float32, node p's vertices in C order of the lattice, its edges to p + (1,0,0) (0,1,0)
+ * (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1) in that order, at origin + (p + t s) * spacing (fp64 arithmetic, rounded on
+ * the store); faces: cap_faces x 3 int32, right-hand normal from inside to outside; normals: cap_vertices x 3 float32 or
+ * null -- the normalised gradient of phi (central differences, one-sided at the lattice border) interpolated along
+ * the edge.                                                                                                      */
+size_t mfs_surface3d_workspace_bytes(const int64_t shape[3], int closed);
+int mfs_surface3d_count(const int64_t shape[3], const void* phi, int phi_dt, double level, int closed, double outside,
+                        void* workspace, size_t workspace_bytes, mfs_stream stream);
+int mfs_surface3d_fill(const int64_t shape[3], const void* phi, int phi_dt, double level, int closed, double outside,
+                       const double origin[3], const double spacing[3], void* workspace, size_t workspace_bytes,
+                       void* vertices, int64_t cap_vertices, void* faces, int64_t cap_faces, void* normals,
+                       mfs_stream stream);
+/* The same one dimension down: every lattice square cut along its (1,1) diagonal, node p's edges to p + (1,0) (0,1)
+ * (1,1); vertices cap_vertices x 2 float32; segments cap_segments x 2 int32, the inside on the left of (u, v).     */
+size_t mfs_contour2d_workspace_bytes(const int64_t shape[2], int closed);
+int mfs_contour2d_count(const int64_t shape[2], const void* phi, int phi_dt, double level, int closed, double outside,
+                        void* workspace, size_t workspace_bytes, mfs_stream stream);
+int mfs_contour2d_fill(const int64_t shape[2], const void* phi, int phi_dt, double level, int closed, double outside,
+                       const double origin[2], const double spacing[2], void* workspace, size_t workspace_bytes,
+                       void* vertices, int64_t cap_vertices, void* segments, int64_t cap_segments, mfs_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -225,6 +225,12 @@ SIGNATURES = {
     "mfs_grid_extrapolate2d_workspace_bytes": (_sz, [_pi64, _i]),
     "mfs_grid_extrapolate2d": (_i, [_pi64, _i, _p, _p, _i, _p, _p, _i, _p, _sz, _p]),
     "mfs_grid_boundary_condition2d": (_i, [_pi64, _p, _p, _i, _p, _p, _i, _p, _i, _p, _i, _d, _p, _p, _i, _p]),
+    "mfs_surface3d_workspace_bytes": (_sz, [_pi64, _i]),
+    "mfs_surface3d_count": (_i, [_pi64, _p, _i, _d, _i, _d, _p, _sz, _p]),
+    "mfs_surface3d_fill": (_i, [_pi64, _p, _i, _d, _i, _d, _pd, _pd, _p, _sz, _p, _i64, _p, _i64, _p, _p]),
+    "mfs_contour2d_workspace_bytes": (_sz, [_pi64, _i]),
+    "mfs_contour2d_count": (_i, [_pi64, _p, _i, _d, _i, _d, _p, _sz, _p]),
+    "mfs_contour2d_fill": (_i, [_pi64, _p, _i, _d, _i, _d, _pd, _pd, _p, _sz, _p, _i64, _p, _i64, _p]),
 }
 
 _lib = None

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 import notebook_kernels as K
+from mfs import surface as _surface
 from mfs.motion import BodyKinematics
 from solver import sdf3D as sdf
 from solver.CGSolverBuffer import CGSolverBuffer
@@ -119,6 +120,12 @@ class NotebookSimulation:
         ds = self.DensitySolver
         self.PressureSolver.solve(g.x.v, g.y.v, g.z.v, sl.phi, sl.v, fl.phi, wx=ds.wx, wy=ds.wy, wz=ds.wz)
         return tick("pressure", t)
+
+    def surface(self, which="liquid", normals=False):
+        """What the notebook plots (marching cubes on the host after scene set-up and after the run), extracted on the GPU:
+        an `mfs.surface.Mesh` of the liquid ({fluid_levelset.phi < 0}, closed against the array border) or of the solid
+        ({solid_levelset.phi < 0} on the doubled grid, open where the solid leaves the bounds)."""
+        return _surface.simulation_surface(self, which, 3, normals=normals)
 
     def step(self, duration_left=float("inf"), timings=None):
         """One pass of the loop body (ipynb:4571-4667, solver == 'apic').  Returns the dt it took."""
@@ -229,6 +236,9 @@ class SlabNotebookSimulation(NotebookSimulation):
                 for arr in (g.x.v, g.y.v, g.z.v):
                     dist.broadcast(arr[a:b], src=r, group=group)
         return tick("gather", t)
+
+    def surface(self, which="liquid", normals=False):
+        raise NotImplementedError("surface() is single-GPU: gather the level set to one rank and call mfs.surface.isosurface")
 
     def close(self):
         self.PressureSolver.close()

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 import notebook_kernels2d as K
+from mfs import surface as _surface
 from mfs.motion import BodyKinematics
 from solver import sdf2D as sdf
 from solver.CGSolverBuffer import CGSolverBuffer
@@ -86,6 +87,11 @@ class NotebookSimulation2D:
         self.ViscositySolver = ViscosityCGSolver2D(g, self.BOUND_SIZE, precision=precision, device=dev)
         self.current_time = 0.0
         self.iterations = 0
+
+    def surface(self, which="liquid"):
+        """`mfs.surface.Contour` of the liquid ({fluid_levelset.phi < 0}, closed against the array border) or of the solid
+        ({solid_levelset.phi < 0} on the doubled grid): `NotebookSimulation.surface` one dimension down."""
+        return _surface.simulation_surface(self, which, 2)
 
     def step(self, duration_left=float("inf"), timings=None):
         """One pass of the loop body.  Returns the dt it took."""
