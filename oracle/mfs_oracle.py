@@ -450,11 +450,14 @@ def _row_views(gres, axis):
     return dg, comp, I
 
 
-def visc_extrapolate3d(gres, num_iter, vx, vy, vz, sphi):
+def visc_extrapolate3d(gres, num_iter, vx, vy, vz, sphi, valid_out=None):
     """solver/ViscosityCGSolver3D.py:8-39,472-502: `num_iter` Jacobi sweeps of the
-    6-neighbour average into invalid (sphi<0) interior faces."""
+    6-neighbour average into invalid (sphi<0) interior faces.  `valid_out`, if a list, receives the
+    three validity arrays as they stand after the last sweep (after none: `sphi >= 0` at the faces)."""
     sphi = np.asarray(sphi, F64)
     valids = [sphi[0::2, 1::2, 1::2] >= 0, sphi[1::2, 0::2, 1::2] >= 0, sphi[1::2, 1::2, 0::2] >= 0]
+    if valid_out is not None:
+        valid_out[:] = valids
     for _ in range(num_iter):
         for v, valid in zip((vx, vy, vz), valids):
             n = v.shape
@@ -477,7 +480,12 @@ def visc_extrapolate3d(gres, num_iter, vx, vy, vz, sphi):
             valid[...] = nv
 
 
-def _visc_row(axis, gres, scale, mu, V, sphi, vol, rhs):
+def _visc_row(axis, gres, scale, mu, V, sphi, vol, rhs, mag=None):
+    """`mag`, if a dict, receives under `axis` a face array holding, on the interior faces, S = |own term| + the sum of
+    |tap term| over the taps that the row adds: every partial sum of the row, in any order, is at most S in magnitude.
+    (0 elsewhere; on solid faces the row is exactly 0.0 and S is not used.)"""
+    if mag is not None:
+        mag[axis] = np.zeros(_face_shape(gres, axis))
     if min(_face_shape(gres, axis)) < 3:
         return (slice(0, 0),) * 3, np.zeros((0, 0, 0))      # no interior face in this row
     dg, comp, I = _row_views(gres, axis)
@@ -493,6 +501,7 @@ def _visc_row(axis, gres, scale, mu, V, sphi, vol, rhs):
         diag = vs["c"] + scale * mu * (m(fR, vs["R"]) + m(fL, vs["L"]) + m(fT, vs["T"])
                                        + m(fB, vs["B"]) + m(fF, vs["F"]) + m(fK, vs["K"]))   # :268
         val = diag * own
+    S = np.abs(val) if mag is not None else None
     for fac, vname, sgn, c, off, moff in row["taps"]:
         k = (2 * scale * mu) if fac == 2 else (scale * mu)
         term = k * vs[vname] * comp(V[c], off)
@@ -501,22 +510,26 @@ def _visc_row(axis, gres, scale, mu, V, sphi, vol, rhs):
             val = val - sgn * np.where(ms < 0, term, 0.0)
         else:
             val = val + sgn * np.where(ms >= 0, term, 0.0)
+        if mag is not None:
+            S = S + np.where((ms < 0) if rhs else (ms >= 0), np.abs(term), 0.0)
+    if mag is not None:
+        mag[axis][I] = S
     return I, np.where(solid, 0.0, val)
 
 
-def visc_rhs3d(gres, scale, mu, vx, vy, vz, sphi, sv, vol, b_x, b_y, b_z):
-    """solver/ViscosityCGSolver3D.py:41-246,504-513.  `sv` is accepted and unused (Q12)."""
+def visc_rhs3d(gres, scale, mu, vx, vy, vz, sphi, sv, vol, b_x, b_y, b_z, mag=None):
+    """solver/ViscosityCGSolver3D.py:41-246,504-513.  `sv` is accepted and unused (Q12).  `mag`: see `_visc_row`."""
     V = (np.asarray(vx, F64), np.asarray(vy, F64), np.asarray(vz, F64))
     for axis, b in enumerate((b_x, b_y, b_z)):
-        I, val = _visc_row(axis, gres, scale, mu, V, np.asarray(sphi, F64), np.asarray(vol, F64), True)
+        I, val = _visc_row(axis, gres, scale, mu, V, np.asarray(sphi, F64), np.asarray(vol, F64), True, mag)
         b[I] = val
 
 
-def visc_apply3d(gres, scale, mu, vx, vy, vz, out_x, out_y, out_z, sphi, vol):
-    """solver/ViscosityCGSolver3D.py:248-456,515-524."""
+def visc_apply3d(gres, scale, mu, vx, vy, vz, out_x, out_y, out_z, sphi, vol, mag=None):
+    """solver/ViscosityCGSolver3D.py:248-456,515-524.  `mag`: see `_visc_row`."""
     V = (np.asarray(vx, F64), np.asarray(vy, F64), np.asarray(vz, F64))
     for axis, o in enumerate((out_x, out_y, out_z)):
-        I, val = _visc_row(axis, gres, scale, mu, V, np.asarray(sphi, F64), np.asarray(vol, F64), False)
+        I, val = _visc_row(axis, gres, scale, mu, V, np.asarray(sphi, F64), np.asarray(vol, F64), False, mag)
         o[I] = val
 
 
@@ -572,10 +585,13 @@ class ViscosityCGSolver3D:
 # the notebook's grid kernels that bracket the two solves
 # (3D_viscous_fluid_sim.ipynb code cells 5 and 7; "ipynb cN:L" = line L of code cell N)
 # =============================================================================
-def nb_extrapolate(gres, num_iter, vx, vy, vz, mx, my, mz):
+def nb_extrapolate(gres, num_iter, vx, vy, vz, mx, my, mz, valid_out=None):
     """ipynb c7:1-64 (`extrapolate`, called at ipynb:4652 with num_iter=2): the same Jacobi
-    sweep as the viscosity solver's, with validity = grid mass > 0 instead of sphi >= 0."""
+    sweep as the viscosity solver's, with validity = grid mass > 0 instead of sphi >= 0.
+    `valid_out` as in `visc_extrapolate3d`."""
     valids = [np.asarray(mx) > 0, np.asarray(my) > 0, np.asarray(mz) > 0]
+    if valid_out is not None:
+        valid_out[:] = valids
     for _ in range(num_iter):
         for v, valid in zip((vx, vy, vz), valids):
             n = v.shape
@@ -597,7 +613,18 @@ def nb_extrapolate(gres, num_iter, vx, vy, vz, mx, my, mz):
             valid[...] = nv
 
 
-def nb_boundary_condition(gres, gv, gm, sphi, sv, dx, dv):
+# boundary_condition_{x,y,z}, per component: the two other components and their 4 (ix, iy) sample offsets, as written in c5
+#   x: vy,gmy at (x-ix, y+iy, z) ; vz,gmz at (x-ix, y, z+iy)
+#   y: vx,gmx at (x+iz, y-iy, z) ; vz,gmz at (x, y-iy, z+iz)
+#   z: vx,gmx at (x+ix, y, z-iz) ; vy,gmy at (x, y+ix, z-iz)
+NB_BC_TAPS = {
+    0: ((1, [(-ix, iy, 0) for ix in range(2) for iy in range(2)]), (2, [(-ix, 0, iy) for ix in range(2) for iy in range(2)])),
+    1: ((0, [(iz, -iy, 0) for iy in range(2) for iz in range(2)]), (2, [(0, -iy, iz) for iy in range(2) for iz in range(2)])),
+    2: ((0, [(ix, 0, -iz) for iz in range(2) for ix in range(2)]), (1, [(0, ix, -iz) for iz in range(2) for ix in range(2)])),
+}
+
+
+def nb_boundary_condition(gres, gv, gm, sphi, sv, dx, dv, mag=None, reverse=False):
     """ipynb c5:1-146 (`boundary_condition_{x,y,z}`): dv = -(component of the solid-relative
     velocity's inward normal part) * (1 - sphi/dx) on interior faces closer than dx to a solid;
     0 elsewhere (array-boundary faces included).  gv, gm, dv are (x,y,z) triples of face arrays.
@@ -609,22 +636,21 @@ def nb_boundary_condition(gres, gv, gm, sphi, sv, dx, dv):
     with the array shape, so threads of the rounded-up launch grid store out of bounds -- on
     the GPU some of those stores race with interior faces of the next plane.  The intended
     (race-free) result is restated here; tests/golden/make_goldens_notebook.py drops those stores.
+
+    `mag`, if a dict, receives under each axis a face array holding, on the interior faces,
+    A = (sum_i |sn_i| (|vel_i| + |sv_i|)) |sn_a| sn_inv |1 - ndist|, with |vel_i| = sum |v m| / msum for the two averaged
+    components: the magnitude that the rounding errors of dv scale with (0 elsewhere; NaN or inf where dv is NaN or where
+    an averaged mass is 0).  `reverse` evaluates every sum in the opposite order (for tests of error bounds).
     """
     sphi = np.asarray(sphi, F64)
     sv = np.asarray(sv, F64)
     D0 = ((0, 1, 1), (1, 0, 1), (1, 1, 0))
-    # per component: the two other components and their 4 (ix, iy) sample offsets, as written in c5
-    #   x: vy,gmy at (x-ix, y+iy, z) ; vz,gmz at (x-ix, y, z+iy)
-    #   y: vx,gmx at (x+iz, y-iy, z) ; vz,gmz at (x, y-iy, z+iz)
-    #   z: vx,gmx at (x+ix, y, z-iz) ; vy,gmy at (x, y+ix, z-iz)
-    taps = {
-        0: ((1, [(-ix, iy, 0) for ix in range(2) for iy in range(2)]), (2, [(-ix, 0, iy) for ix in range(2) for iy in range(2)])),
-        1: ((0, [(iz, -iy, 0) for iy in range(2) for iz in range(2)]), (2, [(0, -iy, iz) for iy in range(2) for iz in range(2)])),
-        2: ((0, [(ix, 0, -iz) for iz in range(2) for ix in range(2)]), (1, [(0, ix, -iz) for iz in range(2) for ix in range(2)])),
-    }
+    taps = NB_BC_TAPS
     for a in range(3):
         n = gv[a].shape
         dv[a][...] = 0
+        if mag is not None:
+            mag[a] = np.zeros(n)
         if min(n) < 3:
             continue
         cnt = tuple(s - 2 for s in n)
@@ -640,23 +666,35 @@ def nb_boundary_condition(gres, gv, gm, sphi, sv, dx, dv):
         ndist = dg(sphi, (0, 0, 0)) / dx
         vel = [None, None, None]
         vel[a] = sh(gv[a], (0, 0, 0)).astype(F64)
+        avel = [None, None, None]
+        avel[a] = np.abs(vel[a])
         with np.errstate(divide="ignore", invalid="ignore"):
             for comp, offs in taps[a]:
                 msum = np.zeros(cnt)
                 vsum = np.zeros(cnt)
-                for off in offs:
+                asum = np.zeros(cnt)
+                for off in (offs[::-1] if reverse else offs):
                     m_ = sh(gm[comp], off)
                     v_ = sh(gv[comp], off)
                     msum = msum + m_.astype(F64)
                     vsum = vsum + (v_ * m_).astype(F64)       # product in the arrays' own dtype
+                    asum = asum + np.abs(v_ * m_).astype(F64)
                 vel[comp] = vsum / msum
+                avel[comp] = asum / msum
             rel = [vel[c] - dg(sv, (0, 0, 0), c) for c in range(3)]
             e = np.eye(3, dtype=int)
             sn = [dg(sphi, tuple(e[c])) - dg(sphi, tuple(-e[c])) for c in range(3)]
-            sn_inv = 1.0 / (sn[0] ** 2 + sn[1] ** 2 + sn[2] ** 2)
-            s = sn[0] * rel[0] + sn[1] * rel[1] + sn[2] * rel[2]
+            if reverse:
+                sn_inv = 1.0 / (sn[2] ** 2 + sn[1] ** 2 + sn[0] ** 2)
+                s = sn[2] * rel[2] + sn[1] * rel[1] + sn[0] * rel[0]
+            else:
+                sn_inv = 1.0 / (sn[0] ** 2 + sn[1] ** 2 + sn[2] ** 2)
+                s = sn[0] * rel[0] + sn[1] * rel[1] + sn[2] * rel[2]
             proj = np.where(s < 0, s, 0.0) * sn[a] * sn_inv
             out = -proj * (1.0 - ndist)
+            if mag is not None:
+                mag[a][I] = (sum(np.abs(sn[c]) * (avel[c] + np.abs(dg(sv, (0, 0, 0), c))) for c in range(3))
+                             * np.abs(sn[a]) * sn_inv * np.abs(1.0 - ndist))
         dv[a][I] = np.where(ndist >= 1, 0.0, out).astype(dv[a].dtype)
 
 
