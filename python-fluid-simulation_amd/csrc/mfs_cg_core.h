@@ -1413,6 +1413,23 @@ static inline int core_poll(CgCore& c, hipStream_t st, int64_t* iters, int* done
   return MFS_OK;
 }
 
+// First half of a poll for an engine with a resident loop form: reads the scalar block into c.pinned (the stream
+// synchronisation of the look).  kErrNotResident there means a resident launch did not get its workgroups together (a
+// shared GPU): it -- and every launch queued behind it -- wrote nothing, so the state is the one the scalar block describes.
+// The flag is cleared, the batch taken back (iter_enq = the iterations that did complete) and *taken_back set: the engine
+// switches the form that failed to its launch-per-phase loop for good, then calls core_poll(..., have_pinned = !*taken_back).
+static inline int core_read_scalars(CgCore& c, hipStream_t st, bool* taken_back) {
+  MFS_HIP_TRY(hipMemcpyAsync(c.pinned, c.scal, MFS_PCG_NSCALARS * sizeof(double), hipMemcpyDeviceToHost, st));
+  MFS_HIP_TRY(hipStreamSynchronize(st));
+  *taken_back = (int)c.pinned[S_ERR] == kErrNotResident;
+  if (*taken_back) {
+    MFS_HIP_TRY(hipMemsetAsync(c.scal + S_ERR, 0, sizeof(double), st));
+    MFS_HIP_TRY(hipMemsetAsync(c.scal + S_DONE, 0, sizeof(double), st));
+    c.iter_enq = (int64_t)c.pinned[S_ITERS];
+  }
+  return MFS_OK;
+}
+
 static inline int64_t core_history(CgCore& c, double* out_host, int64_t cap, hipStream_t st) {
   if (!out_host || cap < 0) { set_error("history: bad argument"); return MFS_E_INVALID; }
   if (hipMemcpyAsync(c.pinned, c.scal, MFS_PCG_NSCALARS * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -1450,6 +1467,45 @@ static inline int core_solve(CgCore& c, double tol, bool zero_x, int64_t max_ite
     enq += n;
     if ((e = core_poll(c, st, &iters, &done, nullptr, nullptr, nullptr))) return e;
   }
+  if (iters_host) *iters_host = iters;
+  return done ? MFS_OK : MFS_NOT_CONVERGED;
+}
+
+// The batched solve of an engine with loop forms of its own (the 3D pressure and viscosity engines): begin(), then batches
+// of iterate(n) with one poll(&iters, &done) -- the only host synchronisation -- between them, then home(iters, done),
+// which settles what the loop form owes.  No look at the scalar block before the loop: launches queued behind a problem
+// that starts converged return at their top.
+//  - resident() true (asked before every batch): the loop stops by itself inside a batch (one launch), so a longer batch
+//    costs nothing but saves the launch, the reload of the state and the look (~25 us, three or four iterations' worth): at
+//    least 1024 iterations per look -- the notebook's solves (300 .. 600 iterations) then cost one look each.
+//  - launch-per-phase loops, SHORT solves (up to 4 x check_every iterations, where a look costs as much as half a dozen
+//    iterations): the first batch is sized by the engine's previous converged solve (*last_iters; consecutive time steps
+//    need about the same number of iterations): last count + 1/8 + 2, so that the solve costs one look, not one per
+//    `check_every`.  Long solves keep the fixed batches: a prediction that overshoots by hundreds of iterations costs more
+//    no-op launches than the looks it saves.
+// Returns MFS_NOT_CONVERGED after max_iter iterations.
+template <typename Begin, typename Iterate, typename Poll, typename Home, typename Resident>
+static inline int core_solve_batched(CgCore& c, int64_t* last_iters, int64_t max_iter, int64_t check_every, int64_t* iters_host,
+                                     Begin begin, Iterate iterate, Poll poll, Home home, Resident resident) {
+  int e;
+  if ((e = begin())) return e;
+  int64_t enq = 0, iters = 0;
+  int done = 0;
+  bool first = true;
+  while (!done && enq < max_iter) {
+    const bool res = resident();
+    int64_t n = std::min(res ? std::max<int64_t>(check_every, 1024) : check_every, max_iter - enq);
+    if (!res && first && *last_iters > 0 && *last_iters <= 4 * check_every)
+      n = std::min<int64_t>(max_iter - enq, std::min<int64_t>(*last_iters + *last_iters / 8 + 2, *last_iters + 256));
+    first = false;
+    if ((e = iterate(n))) return e;
+    if ((e = poll(&iters, &done))) return e;
+    enq = c.iter_enq;        // = enq + n, unless the poll has just taken a batch back (resident launch not resident)
+  }
+  if (max_iter == 0)       // (nothing iterated: the scalar block as begin left it)
+    if ((e = poll(&iters, &done))) return e;
+  if (done) *last_iters = iters;
+  if ((e = home(iters, done != 0))) return e;
   if (iters_host) *iters_host = iters;
   return done ? MFS_OK : MFS_NOT_CONVERGED;
 }

@@ -12,8 +12,12 @@
 // All four are cell-shaped (rows of Nz, 16-byte aligned when Nz%VEC==0), unlike
 // the caller's wz whose rows of Nz+1 break vector alignment.  Same 6 scalars per
 // cell as the reference formulation (v, lphi, wx, wy, wz -> out).
+#include <type_traits>
+#include <utility>
+
 #include "mfs_cg_core.h"
 #include "mfs_pcg_apply.h"
+#include "mfs_pcg_form.h"
 #include "mfs_pcg_slab.h"
 #include "mfs_rccl.h"
 #include "mfs_pcg_resident.h"
@@ -131,123 +135,117 @@ struct mfs_pcg3d {
 // streams of one tile do not all start on the same HBM channel/bank phase.
 static size_t coef_stride(int64_t n, size_t elt) { return align_up((size_t)n * elt, 4096) + 4096 * 3 + 256; }
 
+// ---------------------------------------------------------------- loop form -----
+// Which loop this engine runs, decided HERE and nowhere else, from the engine as it stands at the call (bound pointers,
+// x_owed, slab_loop: never cached across bind / begin).  `phased` is the launch-per-phase form -- what native_apply /
+// native_finish, the slab loop and the settling of a finished solve go by; `kind` is what mfs_pcg3d_iterate runs: the
+// resident small-grid loop (mfs_pcg_resident.h) where that can stand in for `phased`, else `phased` itself.
+enum LoopKind {
+  kLoopResident,     // one resident launch per batch
+  kLoopLean,         // fused stencil launch that also closes the iteration before it (BookArgs) + x/r update without a tail
+  kLoopFused,        // fused stencil launch + x/r update whose last block closes the iteration
+  kLoopPlain,        // three launches: stencil, x/r update, direction update
+  kLoopJacFused,     // opt-in Jacobi loop on the fused stencil launch (operand z = r / diag)
+  kLoopJacPlain      // opt-in Jacobi loop, three launches
+};
+struct LoopForm {
+  LoopKind kind, phased;
+  // the x update is deferred into the next stencil launch (fused forms, symmetric or density operator).  Decided by the fused
+  // launch's shape alone: a Jacobi engine whose b is misaligned runs kLoopJacPlain, which ignores it, and loop_info reports it
+  bool xdef;
+};
+static bool loop_fused(LoopKind k) { return k == kLoopLean || k == kLoopFused || k == kLoopJacFused; }
+
+static LoopForm loop_form(const mfs_pcg3d* h) {
+  auto al = [](const void* p) { return (uintptr_t)p % 16 == 0; };
+  // the fused stencil launch can serve the engine as bound (LDS march, whole 16-byte vectors, aligned CG vectors)
+  const bool shape = h->fuse != 0 && h->variant == 2 && h->vec_ok && al(h->c.d) && al(h->c.q) && al(h->c.r) && h->Ny >= 3 &&
+                     h->Nz >= 3 && h->Nx >= 3;
+  LoopForm f;
+  if (h->jacobi) f.phased = (shape && h->pd < 2 && core_vec_ok(h->c)) ? kLoopJacFused : kLoopJacPlain;
+  else f.phased = !shape ? kLoopPlain : (h->lean != 0 && h->pd < 2) ? kLoopLean : kLoopFused;      // lean: the tail-less form (BookArgs)
+  // deferred x update: prefetch depth 1, x 16-byte aligned.  auto (< 0): on once the CG vectors no longer fit the Infinity
+  // Cache (256^3 fp32: 134.7 -> 130.2 us/iteration, fp64: 295 -> 276); below that the extra streams cost the march more than
+  // the update kernel saves (128^3: +4 %)
+  const bool on = h->defer_x < 0 ? (5.0 * (double)h->n * h->c.elt > 200e6) : (h->defer_x != 0);
+  f.xdef = on && shape && h->pd < 2 && al(h->c.x);
+  // the resident loop: a grid that fits W workgroups' registers, the fused loop's preconditions (aligned vectors,
+  // compressed coefficient classes), no deferred x update pending
+  const bool res = h->resident != 0 && h->res.ok && h->res_ar && loop_fused(f.phased) && !h->slab_loop && h->defer_x <= 0 &&
+                   !h->x_owed && al(h->c.x);
+  f.kind = res ? kLoopResident : f.phased;
+  return f;
+}
+
+// ---------------------------------------------------------------- stencil launch -----
 // xdef: deferred x update rides along.  book: the launch also closes the previous iteration (BookArgs in mfs_pcg_apply.h)
 struct FuseArgs { const void* r; const void* d_old; void* d_new; void* xdef = nullptr; bool book = false; };
 
+// the run-time form -> template arguments: f is called with the form's code (march_code) as a std::integral_constant, for
+// the codes of the reachable table only.  false: the form is not in the table -- no kernel was built for it, nothing is launched
+template <bool VECTOR, class F, size_t... Is>
+static bool march_dispatch(int code, F&& f, std::index_sequence<Is...>) {
+  constexpr auto codes = march_codes<VECTOR>();
+  return ((code == codes[Is] && (f(std::integral_constant<int, codes[Is]>{}), true)) || ...);
+}
+
+static_assert(kMarchBlock == kApplyBlock, "mfs_pcg_form.h sizes the LDS image for the march's workgroup");
+
+// The form is decided by march_form (mfs_pcg_form.h); this computes grid, LDS size and arguments and launches it.  The
+// reachable table of that header has one kernel per entry: 67 for whole vectors, 13 for VEC == 1.
 template <typename T, int VEC>
 static int launch_apply_v(mfs_pcg3d* h, const T* v, T* out, int xb, int xe, int xb2, int xe2, double* partial,
-                          const double* done, hipStream_t st, int* grid_out, const FuseArgs* fz = nullptr) {
+                          const double* done, hipStream_t st, int* grid_out, const FuseArgs* fz) {
   const T *dg = (const T*)h->diag, *cx = (const T*)h->cx, *cy = (const T*)h->cy, *cz = (const T*)h->cz;
   const T* cz2 = (const T*)h->cz2;                 // the density operator's -z weights (asym only)
-  const bool asym = h->asym != 0;
+  MarchInputs in{};
+  in.variant = h->variant; in.nt = h->nt; in.nt_auto = h->nt_auto; in.compress = h->compress; in.pd = h->pd;
+  in.asym = h->asym != 0; in.lane_mask = h->lane_mask; in.vec = VEC > 1; in.elt = sizeof(T); in.n = h->n; in.Nz = h->Nz;
+  // sparse work list (built behind the initial residual of a single-domain solve): the launch's range must be the list's --
+  // all computed planes, one range
+  in.has_list = h->skip_items != nullptr; in.list_range = xb == h->skip_xb && xe == h->skip_xe && xe2 == xb2;
+  in.fused = !fz ? kFusedNone : fz->book ? (fz->xdef ? kFusedXdefBook : kFusedBook) : fz->xdef ? kFusedXdef : kFused;
+  MarchForm f;
+  const int form_status = march_form(in, &f);
+  MFS_REQUIRE(form_status != kFormNeedsVec, "fused direction update needs the vector path");
+  MFS_REQUIRE(form_status != kFormNeedsLds, "the fused direction update needs the LDS march");
   const int nzv = h->Nz / VEC;
   const int64_t ipp = (int64_t)(h->Ny - 2) * nzv;
-  int variant = asym ? std::max(1, h->variant) : h->variant;
-  const size_t lds = 2 * ((size_t)kApplyBlock * VEC + 2 * (size_t)h->Nz) * sizeof(T);
-  if (variant >= 2 && lds > 64 * 1024) variant = 1;          // absurdly long rows: skip the LDS image
   const int xchunk = std::max(0, h->xchunk);   // 0 = no cap on the length of one march
   ApplyArgs a{h->Nx, h->Ny, h->Nz, xb, xe, xchunk, xb2, xe2};
-  // sparse work list (built behind the initial residual of a single-domain solve): the fused launches of the loop visit
-  // only (tile, plane) pairs that compute anything.  The launch's range must be the list's: all computed planes, one range.
-  if (fz && h->skip_items && h->compress != 0 && VEC > 1 && xb == h->skip_xb && xe == h->skip_xe && xe2 == xb2 && variant >= 2) {
-    a.items = h->skip_items; a.runrem = h->skip_runrem; a.count = h->skip_count;
-  }
-  const bool lmask = a.items != nullptr && h->lane_mask && VEC > 1;
+  if (f.listed) { a.items = h->skip_items; a.runrem = h->skip_runrem; a.count = h->skip_count; }
   const int np = (xe - xb) + (xe2 - xb2);
-  if (variant == 0) {
+  if (f.direct) {
     const int64_t items = (int64_t)np * ipp;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(h->grid_apply, (items + kApplyBlock - 1) / kApplyBlock));
     hipLaunchKernelGGL((k_pcg_apply_direct<T, VEC>), dim3(grid), dim3(kApplyBlock), 0, st, v, out, dg, cx, cy, cz, a,
                        partial, done);
     *grid_out = grid;
-  } else {
-    const int64_t tiles = (ipp + kApplyBlock - 1) / kApplyBlock;
-    const int64_t total = tiles * np;                 // (tile, plane) pairs, cut into `grid` equal segments
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(kMaxPartials, h->cus * h->bpc), total));
-    // Nontemporal loads for the once-read coefficient streams pay off only when the
-    // apply's working set (6 arrays) cannot sit in the 256 MiB Infinity Cache anyway;
-    // below that, default caching lets the next iteration hit on-die.  nt < 0 = auto.
-    // bit 0: diag, cz   bit 1: cx   bit 2: cy   -- the once-per-iteration coefficient streams.
-    int nt = h->nt < 0 ? ((6.0 * (double)h->n * sizeof(T) > 200e6) ? h->nt_auto : 0) : (h->nt & 7);
-    const bool comp = h->compress != 0 && VEC > 1;
-    const int pd = (h->pd >= 2 && !asym) ? 2 : 1;
-    // <LDS, NT, COMP, FUSE, PD, ASYM> with the fused operands (null unless fz)
-#define MFS_GO(LDSF, NTV, CMP, FUS, PDV, ASY)                                                                          \
-    hipLaunchKernelGGL((k_pcg_apply_march<T, VEC, LDSF, NTV, CMP, FUS, PDV, ASY>), dim3(grid), dim3(kApplyBlock),      \
-                       LDSF ? lds : 0, st, v, out, dg, cx, cy, cz, h->cls, a, partial, done,                          \
-                       (const T*)(fz ? fz->r : nullptr), (const T*)(fz ? fz->d_old : nullptr),                         \
-                       (T*)(fz ? fz->d_new : nullptr), (const double*)(fz ? h->c.scal + S_BETA : nullptr), cz2)
-#define MFS_GO_NT_CMP(FUS, PDV, ASY)                                                   \
-    do {                                                                               \
-      if (comp) { if (nt) MFS_GO(true, 7, true, FUS, PDV, ASY); else MFS_GO(true, 0, true, FUS, PDV, ASY); }   \
-      else      { if (nt) MFS_GO(true, 7, false, FUS, PDV, ASY); else MFS_GO(true, 0, false, FUS, PDV, ASY); } \
-    } while (0)
-    if (variant == 1) {                               // marching without the LDS image (fallback / A-B)
-      MFS_REQUIRE(fz == nullptr, "the fused direction update needs the LDS march");
-      if (asym) { if (nt) MFS_GO(false, 1, false, false, 1, true); else MFS_GO(false, 0, false, false, 1, true); }
-      else      { if (nt) MFS_GO(false, 1, false, false, 1, false); else MFS_GO(false, 0, false, false, 1, false); }
-    } else if (fz && fz->book) {
-      // fused direction update + the bookkeeping of the previous iteration (PD 1), with or without the deferred x update
-      const BookArgs bk{h->c.scal, h->c.hist, kHistCap, h->c.part_rr, h->c.n_part_rr, (int)((h->c.iter_enq - 1) & 1)};
-#define MFS_GO_BM(NTV, CMP, ASY, XDF, LMK)                                                                            \
-      hipLaunchKernelGGL((k_pcg_apply_march<T, VEC, true, NTV, CMP, true, 1, ASY, XDF, true, LMK>), dim3(grid),        \
-                         dim3(kApplyBlock), lds, st, v, out, dg, cx, cy, cz, h->cls, a, partial, done,                 \
-                         (const T*)fz->r, (const T*)fz->d_old, (T*)fz->d_new, (const double*)nullptr, cz2,             \
-                         (T*)fz->xdef, (const double*)nullptr, bk)
-      // (LMASK only with compressed access, and only when the launch carries the work list)
-#define MFS_GO_B(NTV, CMP, ASY, XDF)                                                                                   \
-      do { if (CMP && lmask) MFS_GO_BM(NTV, CMP, ASY, XDF, CMP); else MFS_GO_BM(NTV, CMP, ASY, XDF, false); } while (0)
-      if (fz->xdef && asym) {      // (the density operator's -z tap and the deferred x update are independent of each other)
-        if (comp) { if (nt) MFS_GO_B(7, true, true, true); else MFS_GO_B(0, true, true, true); }
-        else      { if (nt) MFS_GO_B(7, false, true, true); else MFS_GO_B(0, false, true, true); }
-      } else if (fz->xdef) {
-        if (comp) { if (nt) MFS_GO_B(7, true, false, true); else MFS_GO_B(0, true, false, true); }
-        else      { if (nt) MFS_GO_B(7, false, false, true); else MFS_GO_B(0, false, false, true); }
-      } else if (asym) {
-        if (comp) { if (nt) MFS_GO_B(7, true, true, false); else MFS_GO_B(0, true, true, false); }
-        else      { if (nt) MFS_GO_B(7, false, true, false); else MFS_GO_B(0, false, true, false); }
-      } else {
-        if (comp) { if (nt) MFS_GO_B(7, true, false, false); else MFS_GO_B(0, true, false, false); }
-        else      { if (nt) MFS_GO_B(7, false, false, false); else MFS_GO_B(0, false, false, false); }
-      }
-#undef MFS_GO_B
-#undef MFS_GO_BM
-    } else if (fz && fz->xdef) {
-      // fused direction update + the previous iteration's x update (PD 1 only); symmetric or density operator
-#define MFS_GO_XM(NTV, CMP, ASY, LMK)                                                                                  \
-      hipLaunchKernelGGL((k_pcg_apply_march<T, VEC, true, NTV, CMP, true, 1, ASY, true, false, LMK>), dim3(grid), dim3(kApplyBlock), \
-                         lds, st, v, out, dg, cx, cy, cz, h->cls, a, partial, done, (const T*)fz->r, (const T*)fz->d_old, \
-                         (T*)fz->d_new, (const double*)(h->c.scal + S_BETA), cz2, (T*)fz->xdef,                          \
-                         (const double*)(h->c.scal + S_ALPHA))
-#define MFS_GO_X(NTV, CMP, ASY)                                                                                        \
-      do { if (CMP && lmask) MFS_GO_XM(NTV, CMP, ASY, CMP); else MFS_GO_XM(NTV, CMP, ASY, false); } while (0)
-      if (asym) {
-        if (comp) { if (nt) MFS_GO_X(7, true, true); else MFS_GO_X(0, true, true); }
-        else      { if (nt) MFS_GO_X(7, false, true); else MFS_GO_X(0, false, true); }
-      } else {
-        if (comp) { if (nt) MFS_GO_X(7, true, false); else MFS_GO_X(0, true, false); }
-        else      { if (nt) MFS_GO_X(7, false, false); else MFS_GO_X(0, false, false); }
-      }
-#undef MFS_GO_X
-#undef MFS_GO_XM
-    } else if (asym) {
-      if (fz) MFS_GO_NT_CMP(true, 1, true); else MFS_GO_NT_CMP(false, 1, true);
-    } else if (fz) {
-      if (pd == 2) MFS_GO_NT_CMP(true, 2, false); else MFS_GO_NT_CMP(true, 1, false);
-    } else if (comp || nt == 0 || nt == 7) {
-      if (pd == 2) MFS_GO_NT_CMP(false, 2, false); else MFS_GO_NT_CMP(false, 1, false);
-    } else {                                          // dense access with a partial nontemporal mask (A-B of the hints)
-      switch (nt) {
-        case 1: MFS_GO(true, 1, false, false, 1, false); break;
-        case 3: MFS_GO(true, 3, false, false, 1, false); break;
-        case 5: MFS_GO(true, 5, false, false, 1, false); break;
-        default: MFS_GO(true, 7, false, false, 1, false); break;
-      }
-    }
-#undef MFS_GO_NT_CMP
-#undef MFS_GO
-    *grid_out = grid;
+    MFS_LAUNCH_CHECK();
+    return MFS_OK;
   }
+  const int64_t tiles = (ipp + kApplyBlock - 1) / kApplyBlock;
+  const int64_t total = tiles * np;                 // (tile, plane) pairs, cut into `grid` equal segments
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(kMaxPartials, h->cus * h->bpc), total));
+  const size_t lds = f.lds ? march_lds_bytes(VEC > 1, sizeof(T), h->Nz) : 0;
+  // one argument rule for every form: the fused operands are null unless fused; beta and alpha come from the scalar block
+  // unless the launch closes the previous iteration itself (book: from the r.r partials, BookArgs)
+  const T* fr = (const T*)(fz ? fz->r : nullptr);
+  const T* fd_old = (const T*)(fz ? fz->d_old : nullptr);
+  T* fd_new = (T*)(fz ? fz->d_new : nullptr);
+  T* xdef = (T*)(fz ? fz->xdef : nullptr);
+  const double* beta_ptr = f.fuse && !f.book ? h->c.scal + S_BETA : nullptr;
+  const double* alpha_ptr = f.xdef && !f.book ? h->c.scal + S_ALPHA : nullptr;
+  const BookArgs bk = f.book ? BookArgs{h->c.scal, h->c.hist, kHistCap, h->c.part_rr, h->c.n_part_rr, (int)((h->c.iter_enq - 1) & 1)}
+                             : BookArgs{};
+  const bool launched = march_dispatch<(VEC > 1)>(march_code(f), [&](auto code) {
+    constexpr MarchForm F = march_decode(decltype(code)::value);
+    hipLaunchKernelGGL((k_pcg_apply_march<T, VEC, F.lds, F.nt, F.comp, F.fuse, F.pd, F.asym, F.xdef, F.book, F.lmask>), dim3(grid),
+                       dim3(kApplyBlock), lds, st, v, out, dg, cx, cy, cz, h->cls, a, partial, done, fr, fd_old, fd_new, beta_ptr,
+                       cz2, xdef, alpha_ptr, bk);
+  }, std::make_index_sequence<march_count(VEC > 1)>{});
+  MFS_REQUIRE(launched, "march form outside the reachable table of mfs_pcg_form.h");
+  *grid_out = grid;
   MFS_LAUNCH_CHECK();
   return MFS_OK;
 }
@@ -262,8 +260,7 @@ static int launch_apply(mfs_pcg3d* h, const void* v, void* out, int xb, int xe, 
   const bool vec = h->vec_ok && ((uintptr_t)v % 16 == 0) && ((uintptr_t)out % 16 == 0);
   const double* done = use_done ? h->c.scal + S_DONE : nullptr;
   if (vec) return launch_apply_v<T, VEC>(h, (const T*)v, (T*)out, xb, xe, xb2, xe2, partial, done, st, grid_out, fz);
-  MFS_REQUIRE(fz == nullptr, "fused direction update needs the vector path");
-  return launch_apply_v<T, 1>(h, (const T*)v, (T*)out, xb, xe, xb2, xe2, partial, done, st, grid_out);
+  return launch_apply_v<T, 1>(h, (const T*)v, (T*)out, xb, xe, xb2, xe2, partial, done, st, grid_out, fz);
 }
 
 static int apply_dispatch(mfs_pcg3d* h, const void* v, void* out, int64_t xb, int64_t xe, double* partial,
@@ -579,9 +576,6 @@ int mfs_pcg3d_begin_finish(mfs_pcg3d* h, mfs_stream stream) {
 
 }  // extern "C"
 
-static bool native_fuse_ok(const mfs_pcg3d* h);
-static bool jac_fuse_ok(const mfs_pcg3d* h);
-
 // ---- live chunks of the cell vectors (mfs_cg_core.h LiveMap): a z-vector is DEAD when every computed cell of it is a
 // ZERO row (not fluid: k_pcg_classify) and r = d = 0 there at the start of the loop -- q, r and d then stay exactly 0 for the
 // whole solve.  The fused stencil launch still sweeps every vector (it owns the direction and x updates); the r update,
@@ -630,7 +624,8 @@ static int pcg_build_live(mfs_pcg3d* h, hipStream_t st, bool slab = false) {
   h->skip_items = nullptr; h->skip_runrem = nullptr; h->skip_count = nullptr;
   // (the opt-in Jacobi loop: its fused single-domain form only -- z = r / diag is 0 wherever r is, so a dead vector stays dead)
   if (!h->sparse_vec || !h->compress || !h->vec_ok || !core_vec_ok(h->c) || h->n < h->sparse_min) return MFS_OK;
-  if (h->jacobi && (slab || !jac_fuse_ok(h))) return MFS_OK;
+  const LoopKind phased = loop_form(h).phased;
+  if (h->jacobi && (slab || phased != kLoopJacFused)) return MFS_OK;
   const int vec = h->dt == MFS_F32 ? 4 : 2;
   const int64_t plane_elems = (int64_t)h->Ny * h->Nz;
   if (slab && h->Nx < 3) return MFS_OK;
@@ -649,7 +644,7 @@ static int pcg_build_live(mfs_pcg3d* h, hipStream_t st, bool slab = false) {
   const int64_t gr[3] = {h->Nx, h->Ny, h->Nz};
   const int64_t npairs = (int64_t)tiles * np;
   const bool skip = h->Nx >= 3 && h->Ny >= 3 && np > 0 && npairs > 0 && npairs <= skip_pairs(gr, h->dt) && npairs < 0x7fffffff &&
-                    (slab || native_fuse_ok(h) || jac_fuse_ok(h));
+                    (slab || loop_fused(phased));
   int* tflags = h->skip_ws;
   int* items = tflags + npairs;
   int* runrem = items + npairs;
@@ -721,55 +716,15 @@ static int jac_iteration(mfs_pcg3d* h, hipStream_t st) {
   return MFS_OK;
 }
 
-extern "C" {
-
-int mfs_pcg3d_begin(mfs_pcg3d* h, double tol, mfs_stream stream) {
-  if (h && h->jacobi) {
-    MFS_REQUIRE(h->c.x && h->is_setup, "engine not bound / set up");
-    h->x_owed = false;
-    h->book_pending = false;
-    h->slab_loop = false;
-    h->c.live = LiveMap{nullptr, nullptr, 0};
-    h->skip_items = nullptr; h->skip_runrem = nullptr; h->skip_count = nullptr;
-    if (int e = jac_begin(h, tol, (hipStream_t)stream)) return e;
-    return pcg_build_live(h, (hipStream_t)stream);
-  }
-  if (int e = mfs_pcg3d_begin_local(h, tol, stream)) return e;
-  if (int e = mfs_pcg3d_begin_finish(h, stream)) return e;
-  return pcg_build_live(h, (hipStream_t)stream);      // single-domain solve: the r update sweeps live chunks only
-}
-
-static bool native_fuse_ok(const mfs_pcg3d* h);
-static bool jac_fuse_ok(const mfs_pcg3d* h);
-static bool resident_ok(const mfs_pcg3d* h);
-// deferred x update: fused native loop (symmetric or density operator), prefetch depth 1, x 16-byte aligned
-static bool xdef_ok(const mfs_pcg3d* h) {
-  // auto (< 0): on once the CG vectors no longer fit the Infinity Cache (256^3 fp32: 134.7 -> 130.2 us/iteration,
-  // fp64: 295 -> 276); below that the extra streams cost the march more than the update kernel saves (128^3: +4 %)
-  const bool on = h->defer_x < 0 ? (5.0 * (double)h->n * h->c.elt > 200e6) : (h->defer_x != 0);
-  return on && (native_fuse_ok(h) || jac_fuse_ok(h)) && h->pd < 2 && ((uintptr_t)h->c.x % 16 == 0);
-}
-
-// the fused stencil launch can serve the engine as bound (LDS march, whole 16-byte vectors, aligned CG vectors)
-static bool fuse_shape_ok(const mfs_pcg3d* h) {
-  const bool vec_in = h->vec_ok && ((uintptr_t)h->c.d % 16 == 0) && ((uintptr_t)h->c.q % 16 == 0) &&
-                      ((uintptr_t)h->c.r % 16 == 0);
-  return h->fuse != 0 && h->variant == 2 && vec_in && h->Ny >= 3 && h->Nz >= 3 && h->Nx >= 3;
-}
-static bool native_fuse_ok(const mfs_pcg3d* h) { return fuse_shape_ok(h) && !h->jacobi; }
-// ... and the opt-in Jacobi loop in its fused form (same kernel, operand z = r / diag)
-static bool jac_fuse_ok(const mfs_pcg3d* h) { return fuse_shape_ok(h) && h->jacobi && h->pd < 2; }
-
 // one iteration of the fused Jacobi loop: stencil launch (iteration 0: on d_0 = z_0 as begin left it; afterwards forming
 // d_j = z_j + beta d_{j-1} into the other buffer of {bound d, d2}, the deferred x update riding along), r / z update with
 // the two dot products' partials, one-block bookkeeping
-extern "C++" {
 template <typename T, int VEC>
 static int jac_iteration_fused(mfs_pcg3d* h, hipStream_t st) {
   const int64_t j = h->c.iter_enq;
   void* d_cur = (j & 1) ? h->d2 : h->c.d;
   void* d_prev = (j & 1) ? h->c.d : h->d2;
-  const bool xdef = xdef_ok(h);
+  const bool xdef = loop_form(h).xdef;
   int grid = 0, e;
   if (j == 0) {
     if ((e = apply_dispatch(h, d_cur, h->c.q, 1, h->Nx - 1, h->c.part_dq, 1, st, &grid))) return e;
@@ -797,12 +752,6 @@ static int jac_iteration_fused(mfs_pcg3d* h, hipStream_t st) {
   ++h->c.iter_enq;
   return MFS_OK;
 }
-}  // extern "C++"
-
-// the tail-less form of the fused loop (see BookArgs)
-static bool lean_ok(const mfs_pcg3d* h) {
-  return h->lean != 0 && native_fuse_ok(h) && h->pd < 2;
-}
 
 // The lean loop leaves iteration j open (its r.r partials written, its bookkeeping not) until the stencil launch of
 // j + 1 closes it.  Whoever needs the scalar block complete -- a poll, the end of a batch, a switch of loop form --
@@ -816,82 +765,6 @@ static int pcg_close_pending(mfs_pcg3d* h, hipStream_t st) {
   return MFS_OK;
 }
 
-// the stencil launch of native iteration j = iter_enq: plain for j = 0, else with d_j = r + beta d_{j-1}
-// formed on the fly into the other buffer of the pair {bound d, d2}; beta from the scalar block, or -- lean loop, iteration
-// j - 1 still open -- from the r.r partials, the launch closing j - 1 itself (BookArgs)
-int mfs_pcg3d_native_apply(mfs_pcg3d* h, mfs_stream stream) {
-  MFS_REQUIRE(h && h->c.x && h->is_setup, "engine not bound / set up");
-  hipStream_t st = (hipStream_t)stream;
-  int e;
-  if (!lean_ok(h) && (e = pcg_close_pending(h, st))) return e;
-  if (!native_fuse_ok(h)) return mfs_pcg3d_phase_apply(h, 1, h->Nx - 1, 1, stream);
-  const int64_t j = h->c.iter_enq;
-  void* d_cur = (j & 1) ? h->d2 : h->c.d;
-  void* d_prev = (j & 1) ? h->c.d : h->d2;
-  int grid = 0;
-  if (j == 0) {
-    if ((e = apply_dispatch(h, d_cur, h->c.q, 1, h->Nx - 1, h->c.part_dq, 1, st, &grid))) return e;
-  } else {
-    FuseArgs fz{h->c.r, d_prev, d_cur};
-    if (xdef_ok(h)) fz.xdef = h->c.x;
-    fz.book = h->book_pending;
-    h->book_pending = false;
-    if ((e = apply_dispatch(h, d_cur, h->c.q, 1, h->Nx - 1, h->c.part_dq, 1, st, &grid, 0, 0, &fz))) return e;
-  }
-  h->c.n_part_dq = grid;
-  return MFS_OK;
-}
-
-// the rest of native iteration j: x/r update (d.q folded in) and -- unless the lean loop leaves that to the next
-// stencil launch -- the direction update or its bookkeeping
-int mfs_pcg3d_native_finish(mfs_pcg3d* h, mfs_stream stream) {
-  MFS_REQUIRE(h && h->c.x && h->is_setup, "engine not bound / set up");
-  hipStream_t st = (hipStream_t)stream;
-  int e;
-  if (!native_fuse_ok(h)) {
-    if ((e = core_update_xr(h->c, true, st))) return e;
-    return core_update_d(h->c, true, st);
-  }
-  const int64_t j = h->c.iter_enq;
-  void* d_cur = (j & 1) ? h->d2 : h->c.d;
-  const bool xdef = xdef_ok(h);
-  if (xdef) h->x_owed = true;                    // r only: x += alpha d rides in the next stencil launch
-  if (lean_ok(h)) {
-    if ((e = core_update_xr(h->c, true, st, xdef ? 1 : 0, d_cur))) return e;
-    ++h->c.iter_enq;
-    h->book_pending = true;
-    return MFS_OK;
-  }
-  // the last block of the update closes the iteration (convergence test, history, beta): 2 launches per iteration
-  if (xdef) {
-    XrTail tl{1, h->c.hist, kHistCap, nullptr, 0, 0};
-    if ((e = core_update_xr(h->c, true, st, 1, d_cur, 0, -1, &tl, nullptr))) return e;
-    ++h->c.iter_enq;
-    return MFS_OK;
-  }
-  return core_update_xr_close(h->c, true, st, d_cur, 1);
-}
-
-// n iterations as  A U | A* U | ... | A* U | B : A = fused stencil launch (beta from the scalar block), A* = stencil launch
-// that first closes the iteration before it, U = x/r update without a tail, B = one-block bookkeeping for the last
-// iteration of the batch -- so that the scalar block is complete whenever the host looks.
-static int pcg_iterate_lean(mfs_pcg3d* h, int64_t n, hipStream_t st) {
-  for (int64_t i = 0; i < n; ++i) {
-    int e;
-    if ((e = mfs_pcg3d_native_apply(h, (mfs_stream)st))) return e;
-    if ((e = mfs_pcg3d_native_finish(h, (mfs_stream)st))) return e;
-  }
-  return pcg_close_pending(h, st);
-}
-
-// the resident loop (mfs_pcg_resident.h): a grid that fits W workgroups' registers, the fused loop's preconditions
-// (aligned vectors, compressed coefficient classes), no deferred x update pending
-static bool resident_ok(const mfs_pcg3d* h) {
-  return h->resident != 0 && h->res.ok && h->res_ar && (native_fuse_ok(h) || (jac_fuse_ok(h) && core_vec_ok(h->c))) &&
-         !h->slab_loop && h->defer_x <= 0 && !h->x_owed && ((uintptr_t)h->c.x % 16 == 0);
-}
-
-extern "C++" {
 template <typename T, int VEC>
 static int pcg_launch_resident(mfs_pcg3d* h, const ResArgs& a, hipStream_t st) {
   const ResPlan& p = h->res;
@@ -912,7 +785,6 @@ static int pcg_launch_resident(mfs_pcg3d* h, const ResArgs& a, hipStream_t st) {
   MFS_LAUNCH_CHECK();
   return MFS_OK;
 }
-}  // extern "C++"
 
 static int pcg_iterate_resident(mfs_pcg3d* h, int64_t n, hipStream_t st) {
   while (n > 0) {
@@ -943,43 +815,12 @@ static int pcg_iterate_resident(mfs_pcg3d* h, int64_t n, hipStream_t st) {
   return MFS_OK;
 }
 
-int mfs_pcg3d_iterate(mfs_pcg3d* h, int64_t n, mfs_stream stream) {
-  MFS_REQUIRE(h && h->c.x && h->is_setup, "engine not bound / set up");
-  if (h->jacobi || resident_ok(h) || !lean_ok(h))
-    if (int e = pcg_close_pending(h, (hipStream_t)stream)) return e;
-  if (resident_ok(h)) return pcg_iterate_resident(h, n, (hipStream_t)stream);      // (plain or Jacobi: template flag JAC)
-  if (!h->jacobi && lean_ok(h)) return pcg_iterate_lean(h, n, (hipStream_t)stream);
-  if (h->jacobi && jac_fuse_ok(h) && core_vec_ok(h->c)) {
-    for (int64_t i = 0; i < n; ++i) {
-      const int e = h->dt == MFS_F32 ? jac_iteration_fused<float, 4>(h, (hipStream_t)stream)
-                                     : jac_iteration_fused<double, 2>(h, (hipStream_t)stream);
-      if (e) return e;
-    }
-    return MFS_OK;
-  }
-  if (h->jacobi) {
-    const bool vec = core_vec_ok(h->c) && ((uintptr_t)h->diag % 16 == 0);
-    for (int64_t i = 0; i < n; ++i) {
-      int e;
-      if (h->dt == MFS_F32) e = vec ? jac_iteration<float, 4>(h, (hipStream_t)stream) : jac_iteration<float, 1>(h, (hipStream_t)stream);
-      else e = vec ? jac_iteration<double, 2>(h, (hipStream_t)stream) : jac_iteration<double, 1>(h, (hipStream_t)stream);
-      if (e) return e;
-    }
-    return MFS_OK;
-  }
-  for (int64_t i = 0; i < n; ++i) {   // 3 launches per iteration: the dots are folded into their consumers
-    int e;
-    if ((e = mfs_pcg3d_native_apply(h, stream))) return e;
-    if ((e = mfs_pcg3d_native_finish(h, stream))) return e;
-  }
-  return MFS_OK;
-}
-
 // after a fused native loop the reference's `d` (d of the last completed iteration) may sit in the
 // engine's partner buffer: bring it home to the bound array (iteration count known from a poll)
 static int pcg_home_d(mfs_pcg3d* h, int64_t iters, bool converged, hipStream_t st) {
-  const bool jac = jac_fuse_ok(h) && core_vec_ok(h->c);
-  if (!(native_fuse_ok(h) || jac) || iters < 1 || !h->c.d) return MFS_OK;
+  const LoopKind phased = loop_form(h).phased;
+  const bool jac = phased == kLoopJacFused;
+  if (!loop_fused(phased) || iters < 1 || !h->c.d) return MFS_OK;
   void* cur = ((iters - 1) & 1) ? h->d2 : h->c.d;             // holds d_{iters-1}
   const void* rsrc = jac ? h->zb : h->c.r;                    // fused Jacobi loop: d = z + beta d
   if (h->x_owed) {                                            // owed: x += alpha_{iters-1} d_{iters-1}
@@ -1021,29 +862,132 @@ static int pcg_home_d(mfs_pcg3d* h, int64_t iters, bool converged, hipStream_t s
   return MFS_OK;
 }
 
+extern "C" {
+
+int mfs_pcg3d_begin(mfs_pcg3d* h, double tol, mfs_stream stream) {
+  if (h && h->jacobi) {
+    MFS_REQUIRE(h->c.x && h->is_setup, "engine not bound / set up");
+    h->x_owed = false;
+    h->book_pending = false;
+    h->slab_loop = false;
+    h->c.live = LiveMap{nullptr, nullptr, 0};
+    h->skip_items = nullptr; h->skip_runrem = nullptr; h->skip_count = nullptr;
+    if (int e = jac_begin(h, tol, (hipStream_t)stream)) return e;
+    return pcg_build_live(h, (hipStream_t)stream);
+  }
+  if (int e = mfs_pcg3d_begin_local(h, tol, stream)) return e;
+  if (int e = mfs_pcg3d_begin_finish(h, stream)) return e;
+  return pcg_build_live(h, (hipStream_t)stream);      // single-domain solve: the r update sweeps live chunks only
+}
+
+// the stencil launch of native iteration j = iter_enq: plain for j = 0, else with d_j = r + beta d_{j-1}
+// formed on the fly into the other buffer of the pair {bound d, d2}; beta from the scalar block, or -- lean loop, iteration
+// j - 1 still open -- from the r.r partials, the launch closing j - 1 itself (BookArgs)
+int mfs_pcg3d_native_apply(mfs_pcg3d* h, mfs_stream stream) {
+  MFS_REQUIRE(h && h->c.x && h->is_setup, "engine not bound / set up");
+  hipStream_t st = (hipStream_t)stream;
+  const LoopForm f = loop_form(h);
+  int e;
+  if (f.phased != kLoopLean && (e = pcg_close_pending(h, st))) return e;
+  if (f.phased != kLoopLean && f.phased != kLoopFused) return mfs_pcg3d_phase_apply(h, 1, h->Nx - 1, 1, stream);
+  const int64_t j = h->c.iter_enq;
+  void* d_cur = (j & 1) ? h->d2 : h->c.d;
+  void* d_prev = (j & 1) ? h->c.d : h->d2;
+  int grid = 0;
+  if (j == 0) {
+    if ((e = apply_dispatch(h, d_cur, h->c.q, 1, h->Nx - 1, h->c.part_dq, 1, st, &grid))) return e;
+  } else {
+    FuseArgs fz{h->c.r, d_prev, d_cur};
+    if (f.xdef) fz.xdef = h->c.x;
+    fz.book = h->book_pending;
+    h->book_pending = false;
+    if ((e = apply_dispatch(h, d_cur, h->c.q, 1, h->Nx - 1, h->c.part_dq, 1, st, &grid, 0, 0, &fz))) return e;
+  }
+  h->c.n_part_dq = grid;
+  return MFS_OK;
+}
+
+// the rest of native iteration j: x/r update (d.q folded in) and -- unless the lean loop leaves that to the next
+// stencil launch -- the direction update or its bookkeeping
+int mfs_pcg3d_native_finish(mfs_pcg3d* h, mfs_stream stream) {
+  MFS_REQUIRE(h && h->c.x && h->is_setup, "engine not bound / set up");
+  hipStream_t st = (hipStream_t)stream;
+  const LoopForm f = loop_form(h);
+  int e;
+  if (f.phased != kLoopLean && f.phased != kLoopFused) {
+    if ((e = core_update_xr(h->c, true, st))) return e;
+    return core_update_d(h->c, true, st);
+  }
+  const int64_t j = h->c.iter_enq;
+  void* d_cur = (j & 1) ? h->d2 : h->c.d;
+  if (f.xdef) h->x_owed = true;                  // r only: x += alpha d rides in the next stencil launch
+  if (f.phased == kLoopLean) {
+    if ((e = core_update_xr(h->c, true, st, f.xdef ? 1 : 0, d_cur))) return e;
+    ++h->c.iter_enq;
+    h->book_pending = true;
+    return MFS_OK;
+  }
+  // the last block of the update closes the iteration (convergence test, history, beta): 2 launches per iteration
+  if (f.xdef) {
+    XrTail tl{1, h->c.hist, kHistCap, nullptr, 0, 0};
+    if ((e = core_update_xr(h->c, true, st, 1, d_cur, 0, -1, &tl, nullptr))) return e;
+    ++h->c.iter_enq;
+    return MFS_OK;
+  }
+  return core_update_xr_close(h->c, true, st, d_cur, 1);
+}
+
+int mfs_pcg3d_iterate(mfs_pcg3d* h, int64_t n, mfs_stream stream) {
+  MFS_REQUIRE(h && h->c.x && h->is_setup, "engine not bound / set up");
+  hipStream_t st = (hipStream_t)stream;
+  const LoopKind kind = loop_form(h).kind;
+  int e;
+  if (kind != kLoopLean && (e = pcg_close_pending(h, st))) return e;
+  switch (kind) {
+    case kLoopResident: return pcg_iterate_resident(h, n, st);      // (plain or Jacobi: template flag JAC)
+    case kLoopJacFused:
+      for (int64_t i = 0; i < n; ++i) {
+        e = h->dt == MFS_F32 ? jac_iteration_fused<float, 4>(h, st) : jac_iteration_fused<double, 2>(h, st);
+        if (e) return e;
+      }
+      return MFS_OK;
+    case kLoopJacPlain: {
+      const bool vec = core_vec_ok(h->c) && ((uintptr_t)h->diag % 16 == 0);
+      for (int64_t i = 0; i < n; ++i) {
+        if (h->dt == MFS_F32) e = vec ? jac_iteration<float, 4>(h, st) : jac_iteration<float, 1>(h, st);
+        else e = vec ? jac_iteration<double, 2>(h, st) : jac_iteration<double, 1>(h, st);
+        if (e) return e;
+      }
+      return MFS_OK;
+    }
+    default: break;
+  }
+  // plain: 3 launches per iteration, the dots folded into their consumers.  fused: 2.  lean: n iterations as
+  // A U | A* U | ... | A* U | B : A = fused stencil launch (beta from the scalar block), A* = stencil launch that first closes
+  // the iteration before it, U = x/r update without a tail, B = one-block bookkeeping for the last iteration of the
+  // batch -- so that the scalar block is complete whenever the host looks.
+  for (int64_t i = 0; i < n; ++i) {
+    if ((e = mfs_pcg3d_native_apply(h, stream))) return e;
+    if ((e = mfs_pcg3d_native_finish(h, stream))) return e;
+  }
+  return pcg_close_pending(h, st);
+}
+
 int mfs_pcg3d_poll(mfs_pcg3d* h, mfs_stream stream, int64_t* iters, int* done, double* delta, double* alpha,
                    double* beta) {
   MFS_REQUIRE(h, "null handle");
   hipStream_t st = (hipStream_t)stream;
   if (int e = pcg_close_pending(h, st)) return e;
-  // The resident loop did not get its workgroups together (a shared GPU): that launch -- and every launch queued behind
-  // it -- wrote nothing, so the state is the one the scalar block describes.  Clear the flag, switch this engine to the
-  // launch-per-phase loop for good, and report the iterations that did complete: the caller (mfs_pcg3d_solve does) goes on
-  // from there.
-  MFS_HIP_TRY(hipMemcpyAsync(h->c.pinned, h->c.scal, MFS_PCG_NSCALARS * sizeof(double), hipMemcpyDeviceToHost, st));
-  MFS_HIP_TRY(hipStreamSynchronize(st));
-  bool fresh = true;
-  if ((int)h->c.pinned[S_ERR] == kErrNotResident) {
-    MFS_HIP_TRY(hipMemsetAsync(h->c.scal + S_ERR, 0, sizeof(double), st));
-    MFS_HIP_TRY(hipMemsetAsync(h->c.scal + S_DONE, 0, sizeof(double), st));
-    h->resident = 0;
-    h->c.iter_enq = (int64_t)h->c.pinned[S_ITERS];
-    fresh = false;
-  }
+  // The resident loop did not get its workgroups together (a shared GPU): core_read_scalars takes the batch back; this
+  // engine switches to the launch-per-phase loop for good and reports the iterations that did complete: the caller
+  // (mfs_pcg3d_solve does) goes on from there.
+  bool taken_back = false;
+  if (int e = core_read_scalars(h->c, st, &taken_back)) return e;
+  if (taken_back) h->resident = 0;
   // lane-level masking of the listed launches (mfs_pcg_apply.h LMASK): this solve's decision arrives with the scalar block;
   // launches enqueued from here on -- and the next solve's first batch -- take it (the class marks are per solve either way)
   h->lane_mask = h->c.pinned[S_LANE] != 0.0;
-  return core_poll(h->c, st, iters, done, delta, alpha, beta, fresh);
+  return core_poll(h->c, st, iters, done, delta, alpha, beta, !taken_back);
 }
 
 // what the native loop will do for the engine as bound: bit 0 fused direction update, bit 1 deferred x update, bit 2 Jacobi,
@@ -1051,9 +995,9 @@ int mfs_pcg3d_poll(mfs_pcg3d* h, mfs_stream stream, int64_t* iters, int* done, d
 int mfs_pcg3d_loop_info(mfs_pcg3d* h) {
   if (!h) return 0;
   if (!h->c.x) return h->jacobi ? 4 : 0;          // not bound yet: only the mode is known
-  const bool res = resident_ok(h);
-  const bool jf = jac_fuse_ok(h) && core_vec_ok(h->c);
-  return ((native_fuse_ok(h) || jf) ? 1 : 0) | (!res && xdef_ok(h) ? 2 : 0) | (h->jacobi ? 4 : 0) | (res ? 8 : 0);
+  const LoopForm f = loop_form(h);
+  const bool res = f.kind == kLoopResident;
+  return (loop_fused(f.phased) ? 1 : 0) | (!res && f.xdef ? 2 : 0) | (h->jacobi ? 4 : 0) | (res ? 8 : 0);
 }
 
 int mfs_pcg3d_set_sparse(mfs_pcg3d* h, int on) {
@@ -1098,34 +1042,13 @@ int mfs_pcg3d_solve(mfs_pcg3d* h, double tol, int64_t max_iter, int64_t check_ev
                     int64_t* iters_host) {
   MFS_REQUIRE(h, "null handle");
   MFS_REQUIRE(max_iter >= 0 && check_every >= 1, "max_iter / check_every");
-  if (int e = mfs_pcg3d_begin(h, tol, stream)) return e;
-  int64_t enq = 0, iters = 0;
-  int done = 0;
-  // (no look at the scalar block before the loop: launches queued behind a problem that starts converged return at their top)
-  bool first = true;
-  while (!done && enq < max_iter) {
-    // the resident loop stops by itself inside a batch (one launch), so a longer batch costs nothing but saves the
-    // launch, the reload of the state and the look (a stream synchronisation: ~25 us, three or four iterations' worth): at
-    // least 1024 iterations per look there -- the notebook's solves (300 .. 600 iterations) then cost one look each
-    const int64_t every = resident_ok(h) ? std::max<int64_t>(check_every, 1024) : check_every;
-    int64_t n = std::min(every, max_iter - enq);
-    // launch-per-phase loops, SHORT solves (up to 4 x check_every iterations, where a look at the scalar block costs as much as
-    // half a dozen iterations): the first batch is sized by this engine's previous solve -- consecutive time steps need about
-    // the same number of iterations -- so that the solve costs one look, not one per `check_every`.  (Long solves keep the
-    // fixed batches: a prediction that overshoots by hundreds of iterations costs more no-op launches than the looks it saves.)
-    if (first && h->last_iters > 0 && h->last_iters <= 4 * check_every && !resident_ok(h))
-      n = std::min<int64_t>(max_iter - enq, std::min<int64_t>(h->last_iters + h->last_iters / 8 + 2, h->last_iters + 256));
-    first = false;
-    if (int e = mfs_pcg3d_iterate(h, n, stream)) return e;
-    if (int e = mfs_pcg3d_poll(h, stream, &iters, &done, nullptr, nullptr, nullptr)) return e;
-    enq = h->c.iter_enq;        // = enq + n, unless the poll has just taken a batch back (resident loop not resident)
-  }
-  if (max_iter == 0)       // (nothing iterated: the scalar block as begin left it)
-    if (int e = mfs_pcg3d_poll(h, stream, &iters, &done, nullptr, nullptr, nullptr)) return e;
-  if (done) h->last_iters = iters;
-  if (int e = pcg_home_d(h, iters, done != 0, (hipStream_t)stream)) return e;
-  if (iters_host) *iters_host = iters;
-  return done ? MFS_OK : MFS_NOT_CONVERGED;
+  hipStream_t st = (hipStream_t)stream;
+  return core_solve_batched(
+      h->c, &h->last_iters, max_iter, check_every, iters_host, [&] { return mfs_pcg3d_begin(h, tol, stream); },
+      [&](int64_t n) { return mfs_pcg3d_iterate(h, n, stream); },
+      [&](int64_t* iters, int* done) { return mfs_pcg3d_poll(h, stream, iters, done, nullptr, nullptr, nullptr); },
+      [&](int64_t iters, bool converged) { return pcg_home_d(h, iters, converged, st); },
+      [&] { return loop_form(h).kind == kLoopResident; });
 }
 
 int64_t mfs_pcg3d_history(mfs_pcg3d* h, double* out_host, int64_t cap, mfs_stream stream) {
@@ -1141,7 +1064,7 @@ int64_t mfs_pcg3d_history(mfs_pcg3d* h, double* out_host, int64_t cap, mfs_strea
 // ----------------------------------------------------------------------------------------------
 static bool slab_ok(const mfs_pcg3d* h) {
   // (the opt-in Jacobi loop too, in its fused form: the same kernels with z = r / diag as the operand of the direction update)
-  return h->p2p && h->p2p->connected && (native_fuse_ok(h) || (jac_fuse_ok(h) && core_vec_ok(h->c))) &&
+  return h->p2p && h->p2p->connected && loop_fused(loop_form(h).phased) &&
          (size_t)h->Ny * h->Nz * h->c.elt == h->p2p->plane_bytes;
 }
 
@@ -1167,7 +1090,7 @@ static int slab_iteration(mfs_pcg3d* h, hipStream_t st) {
   const T* rsrc = (const T*)(jac ? h->zb : h->c.r);
   const int64_t ep_dq = jac ? 3 * j + 2 : 2 * j + 1, ep_rr = jac ? 3 * j + 3 : 2 * j + 2, ep_rz = 3 * j + 4;
   // deferred x update (as in the native loop): x += alpha_{j-1} d_{j-1} rides in this iteration's edge / interior launches
-  const bool xdef = xdef_ok(h) && L - 2 > 2;
+  const bool xdef = loop_form(h).xdef && L - 2 > 2;
   // 1. edge planes of d_j: local + into the neighbours' windows -- on the second stream, behind everything
   //    the main stream has done so far (beta, r of the previous iteration)
   mfs_rccl* const rc = h->rccl;      // collective transport: RCCL moves the planes and sums the dot products between the launches

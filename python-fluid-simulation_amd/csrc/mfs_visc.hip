@@ -2177,53 +2177,28 @@ int mfs_vcg3d_poll(mfs_vcg3d* h, mfs_stream stream, int64_t* iters, int* done, d
                    double* beta) {
   MFS_REQUIRE(h, "null handle");
   hipStream_t st = (hipStream_t)stream;
-  // The merged vector-phase launch did not get its workgroups together (a shared GPU): it -- and every launch queued behind
-  // it -- wrote nothing to the CG vectors, so the state is the one the scalar block describes.  Clear the flag, switch
-  // this engine to the launch-per-phase loop for good, and report the iterations that did complete.
-  MFS_HIP_TRY(hipMemcpyAsync(h->c.pinned, h->c.scal, MFS_PCG_NSCALARS * sizeof(double), hipMemcpyDeviceToHost, st));
-  MFS_HIP_TRY(hipStreamSynchronize(st));
-  bool fresh = true;
-  if ((int)h->c.pinned[S_ERR] == kErrNotResident) {
-    MFS_HIP_TRY(hipMemsetAsync(h->c.scal + S_ERR, 0, sizeof(double), st));
-    MFS_HIP_TRY(hipMemsetAsync(h->c.scal + S_DONE, 0, sizeof(double), st));
+  // The merged vector-phase launch (or the resident loop) did not get its workgroups together: core_read_scalars takes the
+  // batch back; this engine switches whichever of the two was running to the launch-per-phase loop for good, and reports
+  // the iterations that did complete.
+  bool taken_back = false;
+  if (int e = core_read_scalars(h->c, st, &taken_back)) return e;
+  if (taken_back) {
     if (vcg_resident_ok(h)) h->resident = 0;      // the resident loop did not get its workgroups: launch-per-phase from now on
     else h->c.rdx = 0;
-    h->c.iter_enq = (int64_t)h->c.pinned[S_ITERS];
-    fresh = false;
   }
-  return core_poll(h->c, st, iters, done, delta, alpha, beta, fresh);
+  return core_poll(h->c, st, iters, done, delta, alpha, beta, !taken_back);
 }
 
 int mfs_vcg3d_solve(mfs_vcg3d* h, double tol, int64_t max_iter, int64_t check_every, mfs_stream stream,
                     int64_t* iters_host) {
   MFS_REQUIRE(h, "null handle");
   MFS_REQUIRE(max_iter >= 0 && check_every >= 1, "max_iter / check_every");
-  if (int e = mfs_vcg3d_begin(h, tol, stream)) return e;
-  int64_t enq = 0, iters = 0;
-  int done = 0;
-  // SHORT solves (up to 4 x check_every iterations): the first batch is sized by the previous solve of this engine
-  // (consecutive time steps need about the same number of iterations): last count + 1/8 + 2 in one go, so that the solve costs
-  // ONE look at the scalar block instead of one per `check_every` iterations (launches queued behind a converged iteration
-  // return at their top; a problem that starts converged is caught by them as well).  Later batches, and long solves --
-  // where an overshooting prediction costs more no-op launches than the looks it saves --: `check_every` as before.
-  bool first = true;
-  while (!done && enq < max_iter) {
-    // (the resident loop stops by itself inside a batch -- one launch --: at least 1024 iterations per look there)
-    const bool res = vcg_resident_ok(h);
-    int64_t n = std::min(res ? std::max<int64_t>(check_every, 1024) : check_every, max_iter - enq);
-    if (!res && first && h->last_iters > 0 && h->last_iters <= 4 * check_every)
-      n = std::min<int64_t>(max_iter - enq, std::min<int64_t>(h->last_iters + h->last_iters / 8 + 2, h->last_iters + 256));
-    first = false;
-    if (int e = mfs_vcg3d_iterate(h, n, stream)) return e;
-    if (int e = mfs_vcg3d_poll(h, stream, &iters, &done, nullptr, nullptr, nullptr)) return e;
-    enq = h->c.iter_enq;        // = enq + n, unless the poll has just taken a batch back (merged launch not resident)
-  }
-  if (max_iter == 0)       // (nothing iterated: the scalar block as begin left it)
-    if (int e = mfs_vcg3d_poll(h, stream, &iters, &done, nullptr, nullptr, nullptr)) return e;
-  if (done) h->last_iters = iters;
-  if (int e = vcg_home(h, iters, done != 0, (hipStream_t)stream)) return e;
-  if (iters_host) *iters_host = iters;
-  return done ? MFS_OK : MFS_NOT_CONVERGED;
+  hipStream_t st = (hipStream_t)stream;
+  return core_solve_batched(
+      h->c, &h->last_iters, max_iter, check_every, iters_host, [&] { return mfs_vcg3d_begin(h, tol, stream); },
+      [&](int64_t n) { return mfs_vcg3d_iterate(h, n, stream); },
+      [&](int64_t* iters, int* done) { return mfs_vcg3d_poll(h, stream, iters, done, nullptr, nullptr, nullptr); },
+      [&](int64_t iters, bool converged) { return vcg_home(h, iters, converged, st); }, [&] { return vcg_resident_ok(h); });
 }
 
 // for callers that drive begin / iterate themselves: settles what the fused loop owes (the last x update, the direction
@@ -2237,7 +2212,6 @@ int mfs_vcg3d_finish(mfs_vcg3d* h, mfs_stream stream) {
   return vcg_home(h, iters, done != 0, (hipStream_t)stream);
 }
 
-// 1 / 0: fold the direction and x updates into the marching kernel (default 0; MFS_VISC_FUSE)
 int mfs_vcg3d_set_compress(mfs_vcg3d* h, int on) {
   MFS_REQUIRE(h, "null handle");
   h->compress = on ? 1 : 0;
@@ -2295,6 +2269,7 @@ int mfs_vcg3d_sparse_info(mfs_vcg3d* h, mfs_stream stream, int64_t out[4]) {
   return MFS_OK;
 }
 
+// 1 / 0: fold the direction and x updates into the marching kernel (default 0; MFS_VISC_FUSE)
 int mfs_vcg3d_set_fuse(mfs_vcg3d* h, int on) {
   MFS_REQUIRE(h, "null handle");
   MFS_REQUIRE(!h->fused_run, "mfs_vcg3d_set_fuse inside a fused loop: call mfs_vcg3d_finish first");
