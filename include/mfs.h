@@ -754,6 +754,42 @@ int mfs_contour2d_fill(const int64_t shape[2], const void* phi, int phi_dt, doub
                        const double origin[2], const double spacing[2], void* workspace, size_t workspace_bytes,
                        void* vertices, int64_t cap_vertices, void* segments, int64_t cap_segments, mfs_stream stream);
 
+/* ------------------------------------------------------------------------- */
+/* Triangle-mesh solids (csrc/mfs_meshsdf.hip; DESIGN.md "Triangle-mesh solids") */
+/* ------------------------------------------------------------------------- */
+/* No reference counterpart: the reference's scenes are spheres, boxes and cylinders.  Additions: the ABI version stays.
+ * A lattice is shape[0] x shape[1] x shape[2] nodes in C order (every extent >= 2, fewer than 2^31 nodes), node (i,j,k)
+ * at origin + (i,j,k) * spacing.  triangles: num_triangles x 9 float32, the three corners of each.
+ * _distance3d: phi (float32) = the exact distance of every node to the nearest triangle, fp32 arithmetic, squared
+ * distances compared and one square root at the end; zero-area triangles are skipped.  One workgroup owns a brick of
+ * 4 x 8 x 8 nodes; cull != 0 drops, per brick, the triangles that provably cannot carry a minimum there -- bitwise the
+ * same phi as cull == 0.  survivors: null, or mfs_meshsdf_bricks3d(shape) int32, the triangles each brick looped over.
+ * _sign3d: phi must hold _distance3d's output (>= 0).  Nodes inside the closed surface get the sign bit, by the parity
+ * of crossings of the ray along axis 0, ties broken half-open; odd_columns: shape[1] x shape[2] int32, 1 where a
+ * column's total crossing count is odd (the surface is not closed there).  No atomics in either.                    */
+int64_t mfs_meshsdf_bricks3d(const int64_t shape[3]);
+int mfs_meshsdf_distance3d(const int64_t shape[3], const double origin[3], double spacing, const void* triangles,
+                           int64_t num_triangles, int cull, void* phi, void* survivors, mfs_stream stream);
+int mfs_meshsdf_sign3d(const int64_t shape[3], const double origin[3], double spacing, const void* triangles,
+                       int64_t num_triangles, void* phi, void* odd_columns, mfs_stream stream);
+/* Mesh bodies: num_bodies <= 16 rows of the packed (10,4) float64 layout of mfs_sdf_* (mesh_rb: translation rows 1-4,
+ * rotation rows 5-8, velocity row 9; row 0 is not read), each with a float32 signed-distance volume in its own frame.
+ * The *_host arrays are HOST memory, read before the launch: volumes_host[i] the DEVICE pointer of body i's volume,
+ * extents_host 3 int64 per body, origins_host 3 doubles per body, spacings_host one double per body.  A volume is
+ * sampled trilinearly at x_b = R^T (x - T); outside it: the sample at the clamped point plus the distance to its box.
+ * _union_grid3d: the grid of mfs_sdf_evaluate_grid3d (same position rule).  For every node and every body in turn:
+ * d < sd -> sd = d and vel = (d <= 0 ? row 9 + w x (x - T) : 0); rb_w: num_bodies x 3 float64 or null.  sd / vel hold
+ * the level set the bodies are united with on entry; nodes no body wins are not written.
+ * _project3d: in place; for every body in turn a position with sampled d < 0 moves by -d * R n, n the normalised gradient
+ * of the sampled volume (central differences one spacing apart where it vanishes; still zero: left alone).          */
+int mfs_mesh_union_grid3d(const void* mesh_rb, const void* rb_w, int64_t num_bodies, const void* const* volumes_host,
+                          const int64_t* extents_host, const double* origins_host, const double* spacings_host,
+                          const int64_t res[3], const double bound_min[3], const double bias[3],
+                          const double cell_size[3], void* sd, int sd_dt, void* vel, int vel_dt, mfs_stream stream);
+int mfs_mesh_project3d(const void* mesh_rb, int64_t num_bodies, const void* const* volumes_host,
+                       const int64_t* extents_host, const double* origins_host, const double* spacings_host,
+                       void* position, int pos_dt, int64_t num_positions, mfs_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -231,6 +231,11 @@ SIGNATURES = {
     "mfs_contour2d_workspace_bytes": (_sz, [_pi64, _i]),
     "mfs_contour2d_count": (_i, [_pi64, _p, _i, _d, _i, _d, _p, _sz, _p]),
     "mfs_contour2d_fill": (_i, [_pi64, _p, _i, _d, _i, _d, _pd, _pd, _p, _sz, _p, _i64, _p, _i64, _p]),
+    "mfs_meshsdf_bricks3d": (_i64, [_pi64]),
+    "mfs_meshsdf_distance3d": (_i, [_pi64, _pd, _d, _p, _i64, _i, _p, _p, _p]),
+    "mfs_meshsdf_sign3d": (_i, [_pi64, _pd, _d, _p, _i64, _p, _p, _p]),
+    "mfs_mesh_union_grid3d": (_i, [_p, _p, _i64, C.POINTER(_p), _pi64, _pd, _pd, _pi64, _pd, _pd, _pd, _p, _i, _p, _i, _p]),
+    "mfs_mesh_project3d": (_i, [_p, _i64, C.POINTER(_p), _pi64, _pd, _pd, _p, _i, _i64, _p]),
 }
 
 _lib = None

@@ -47,6 +47,53 @@ class Mesh(NamedTuple):
                     fh.write(f"f {a} {b} {c}\n")
 
 
+def read_obj(path):
+    """Wavefront OBJ -> (vertices float32 (V,3), faces int32 (F,3)), on the host.  `v` and `f` records only; corners in
+    the forms i, i/t, i//n, i/t/n, 1-based or negative (relative to the vertices read so far); polygons are
+    fan-triangulated about their first corner (orientation kept); every other record and comments are ignored.
+    ValueError with the line number on a malformed face or an index out of range."""
+    verts, faces, lines = [], [], []
+    with open(path) as fh:
+        for ln, line in enumerate(fh, 1):
+            rec = line.split("#", 1)[0].split()
+            if not rec:
+                continue
+            if rec[0] == "v":
+                try:
+                    verts.append([float(c) for c in rec[1:4]])
+                    if len(verts[-1]) != 3:
+                        raise ValueError
+                except ValueError:
+                    raise ValueError(f"{path}:{ln}: malformed vertex {line.strip()!r}") from None
+            elif rec[0] == "f":
+                if len(rec) < 4:
+                    raise ValueError(f"{path}:{ln}: a face needs at least three corners, got {line.strip()!r}")
+                idx = []
+                for corner in rec[1:]:
+                    try:
+                        i = int(corner.split("/")[0])
+                    except ValueError:
+                        raise ValueError(f"{path}:{ln}: malformed face corner {corner!r}") from None
+                    j = i - 1 if i > 0 else len(verts) + i          # negative: relative to the vertices read so far
+                    if i == 0 or j < 0:
+                        raise ValueError(f"{path}:{ln}: vertex index {i} out of range ({len(verts)} vertices so far)")
+                    idx.append(j)
+                faces.extend([idx[0], idx[k], idx[k + 1]] for k in range(1, len(idx) - 1))
+                lines.extend([ln] * (len(idx) - 2))
+    faces = np.asarray(faces, np.int64).reshape(-1, 3)
+    bad = np.nonzero((faces >= len(verts)).any(axis=1))[0]    # a positive index may point ahead: checked against the file
+    if len(bad):
+        raise ValueError(f"{path}:{lines[bad[0]]}: vertex index {int(faces[bad[0]].max()) + 1} out of range "
+                         f"({len(verts)} vertices)")
+    return np.asarray(verts, np.float32).reshape(-1, 3), faces.astype(np.int32)
+
+
+def load_obj(path, device="cuda"):
+    """`read_obj` as a `Mesh` of GPU tensors; normals is None"""
+    v, f = read_obj(path)
+    return Mesh(torch.as_tensor(v, device=device), torch.as_tensor(f, device=device), None)
+
+
 class Contour(NamedTuple):
     """vertices (V,2) float32, segments (S,2) int32: the inside lies on the left of every segment (u, v)"""
     vertices: torch.Tensor

@@ -43,12 +43,17 @@ class NotebookSimulation:
     gres, gdx: cell grid and spacing; bound_min: float32 triple; rb_d: packed rigid bodies (solver.sdf3D);
     px: (P,3) float64 particle positions; pdx: particle spacing (mass = rho * pdx^3, volume = pdx^3)."""
 
+    mesh_bodies = mesh_rb = mesh_kinematics = None       # set by __init__(..., mesh_bodies=[...])
+
     def __init__(self, gres, gdx, bound_min, rb_d, px, pdx, rho=1000.0, mu=1.0, dt=1.0 / 300.0, device="cuda",
-                 precision=None, jacobi=False, motion=None):
+                 precision=None, jacobi=False, motion=None, mesh_bodies=None):
         """jacobi=True: the build's opt-in Jacobi preconditioning for the viscosity and pressure solves (NOT the reference's
         iterations -- same stopping rules, a fraction of the CG iterations; single-GPU class only)
         motion: {body index: mfs.motion.Motion} -- those bodies move; `rb_d` is updated in place every step and the solid
-        level set and velocity are re-evaluated at the new pose (`_move_solids`).  None: solids are static scene data."""
+        level set and velocity are re-evaluated at the new pose (`_move_solids`).  None: solids are static scene data.
+        mesh_bodies: a list of `solver.sdf3D.MeshBody` -- closed triangle meshes as solids, united with the bodies of `rb_d`
+        (`sdf.union_mesh_grid`) and kept free of particles every step (`sdf.project_mesh`); one that carries
+        `motion=Motion(...)` moves like the analytic ones.  None: the class runs as it did without them."""
         dev = torch.device(device)
         g = tuple(int(v) for v in gres)
         self.GRES, self.GDX, self.PDX, self.RHO, self.MU, self.DT = g, float(gdx), float(pdx), float(rho), float(mu), float(dt)
@@ -79,6 +84,8 @@ class NotebookSimulation:
                                  v=torch.zeros(dres + (3,), dtype=torch.float64, device=dev))
         self.solid_levelset.pos = grid_positions(dres, bmin, dcs, self.solid_levelset.bias, dev)
         sdf.evaluate(rb_d, self.solid_levelset.phi, self.solid_levelset.v, self.solid_levelset.pos)
+        if mesh_bodies:
+            self._add_mesh_bodies(mesh_bodies)
         self.fluid_levelset = NS(resolution=g, bound_size=bsz, bound_min=bmin, cell_size=cs,
                                  phi=torch.zeros(g, dtype=torch.float64, device=dev))
         self.fluid_volume = NS(resolution=dres, bound_size=bsz, bound_min=bmin, cell_size=dcs,
@@ -102,13 +109,33 @@ class NotebookSimulation:
             self.ViscositySolver._engine.set_jacobi(True)
             self.DensitySolver._engine.set_jacobi(True)      # (the pressure engine with the density operator's -z tap)
 
+    def _add_mesh_bodies(self, mesh_bodies):
+        """the mesh bodies' rows in a table of their own, united with the level set `sdf.evaluate` left"""
+        sl = self.solid_levelset
+        self.mesh_bodies = list(mesh_bodies)
+        if not all(isinstance(b, sdf.MeshBody) for b in self.mesh_bodies):
+            raise TypeError("mesh_bodies: expected a list of solver.sdf3D.MeshBody")
+        self.mesh_rb = sdf.mesh_rb(self.mesh_bodies, self.device)
+        moving = {k: b.motion for k, b in enumerate(self.mesh_bodies) if b.motion is not None}
+        self.mesh_kinematics = BodyKinematics(self.mesh_rb, moving, 3) if moving else None
+        sdf.union_mesh_grid(self.mesh_rb, self.mesh_bodies, sl.phi, sl.v, sl.bound_min, sl.cell_size, sl.bias)
+
     def _move_solids(self, t0, dt, tick, t):
         """bodies to their pose at t0 + dt, particles out of them, solid level set and surface velocity at the new pose"""
         sl = self.solid_levelset
-        self.kinematics.advance(t0, dt)
+        if self.kinematics is not None:
+            self.kinematics.advance(t0, dt)
+        if self.mesh_kinematics is not None:
+            self.mesh_kinematics.advance(t0, dt)
         sdf.project(self.rb_d, self.particle.x)
+        if self.mesh_bodies:
+            sdf.project_mesh(self.mesh_rb, self.mesh_bodies, self.particle.x)
         t = tick("advect+project", t)
-        sdf.evaluate_grid(self.rb_d, sl.phi, sl.v, sl.bound_min, sl.cell_size, sl.bias, rb_w=self.kinematics.rb_w)
+        sdf.evaluate_grid(self.rb_d, sl.phi, sl.v, sl.bound_min, sl.cell_size, sl.bias,
+                          rb_w=None if self.kinematics is None else self.kinematics.rb_w)
+        if self.mesh_bodies:
+            sdf.union_mesh_grid(self.mesh_rb, self.mesh_bodies, sl.phi, sl.v, sl.bound_min, sl.cell_size, sl.bias,
+                                rb_w=None if self.mesh_kinematics is None else self.mesh_kinematics.rb_w)
         return tick("solid", t)
 
     def _solve_grid(self, dt, tick, t):
@@ -144,12 +171,16 @@ class NotebookSimulation:
         t0 = self.current_time
         if self.kinematics is not None:                                     # a body crosses at most one cell per step
             dt = min(dt, self.GDX / max(1e-10, self.kinematics.max_surface_speed(t0)))
+        if self.mesh_kinematics is not None:
+            dt = min(dt, self.GDX / max(1e-10, self.mesh_kinematics.max_surface_speed(t0)))
         self.current_time += dt
         p.x += p.v * dt
-        if self.kinematics is not None:
+        if self.kinematics is not None or self.mesh_kinematics is not None:
             t = self._move_solids(t0, dt, tick, t)
         else:
             sdf.project(self.rb_d, p.x)
+            if self.mesh_bodies:
+                sdf.project_mesh(self.mesh_rb, self.mesh_bodies, p.x)
             t = tick("advect+project", t)
         K.compute_fluid_levelset(p, fl, self.GDX)
         K.compute_fluid_volume(p, fv, p.vol)
@@ -189,6 +220,8 @@ class SlabNotebookSimulation(NotebookSimulation):
     particles (migration between slabs) is the next step.  `step` is collective."""
 
     def __init__(self, *args, dist, group=None, transport="auto", motion=None, **kw):
+        if kw.get("mesh_bodies"):
+            raise NotImplementedError("mesh_bodies: triangle-mesh solids need the single-GPU NotebookSimulation")
         if motion:
             raise ValueError("motion: the slab / sharded time steps treat solids as static scene data; moving bodies need "
                              "the single-GPU NotebookSimulation")

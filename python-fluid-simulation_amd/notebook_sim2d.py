@@ -43,7 +43,9 @@ class NotebookSimulation2D:
     set and velocity are re-evaluated at the new pose.  None: solids are static scene data."""
 
     def __init__(self, gres, gdx, bound_min, rb_d, px, pdx, rho=1000.0, mu=1.0, dt=1.0 / 300.0, device="cuda",
-                 precision=None, motion=None):
+                 precision=None, motion=None, mesh_bodies=None):
+        if mesh_bodies:
+            raise NotImplementedError("mesh_bodies: triangle-mesh solids are 3D and single-GPU (NotebookSimulation)")
         dev = torch.device(device)
         g = tuple(int(v) for v in gres)
         if len(g) != 2:

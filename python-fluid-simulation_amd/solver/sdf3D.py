@@ -4,6 +4,8 @@ description (`generate_rb`, `transform_rb`, `set_vel_rb`, `get_T`, `get_R` -- ho
 body velocity at a set of points; ipynb scene set-up) and `project` (push particles out of / into
 the bodies; ipynb:4584, every step).  PyTorch-ROCm tensors, HIP kernels behind the C ABI; no CPU path.
 """
+import ctypes
+
 import numpy as np
 import torch
 from scipy.spatial.transform import Rotation as R
@@ -124,3 +126,89 @@ def project(rb_d, position):
     lib = _lib.load()
     _lib.check(lib.mfs_sdf_project3d(T.ptr(rb_d), int(rb_d.shape[0]), T.ptr(position), T.code(position),
                                      int(position.numel() // 3), T.stream()), "mfs_sdf_project3d")
+
+
+# ------------------------------------------------------------------ triangle-mesh bodies (no reference counterpart) ----
+MESH_TYPE_CODE = 6        # row 0 of a mesh body; unknown to evaluate / evaluate_grid / project, which leave such rows alone
+MAX_MESH_BODIES = 16      # the volumes' descriptions travel by value in the launch (csrc/mfs_meshsdf.hip)
+
+
+class MeshBody:
+    """A closed triangle mesh as a solid: `sdf` is its `mfs.meshsdf.MeshSDF` (built once), the pose one row of the packed
+    (1, 10, 4) layout -- row 0 = [6, sdf.radius, 0, 0], rows 1-4 translation, rows 5-8 rotation (`axis`, `angle` in
+    degrees, as generate_rb), row 9 velocity -- so that `mfs.motion.BodyKinematics` moves it like any other body.
+    motion: an optional `mfs.motion.Motion`, read by `NotebookSimulation(..., mesh_bodies=[...])`."""
+
+    def __init__(self, sdf, center=(0, 0, 0), axis=(0, 1, 0), angle=0, velocity=(0, 0, 0), motion=None):
+        phi = T.dev(sdf.phi, "sdf.phi")
+        if phi.dim() != 3 or phi.dtype != torch.float32 or min(phi.shape) < 2:
+            raise ValueError("sdf.phi: expected a float32 volume (n0, n1, n2), every extent >= 2")
+        self.sdf, self.motion = sdf, motion
+        row = np.zeros((1, 10, 4))
+        row[0, 0, 0], row[0, 0, 1] = MESH_TYPE_CODE, float(sdf.radius)
+        row[0, 1:5, :] = get_T(center)
+        row[0, 5:9, :] = get_R(list(axis), angle)
+        row[0, 9, :3] = np.asarray(T.as_f64_list(velocity, 3))
+        self.row = row
+
+
+def mesh_rb(bodies, device=None):
+    """the (m, 10, 4) float64 table of the mesh bodies' rows, on the device of their volumes"""
+    bodies = list(bodies)
+    if not bodies:
+        raise ValueError("mesh bodies: an empty list")
+    dev = torch.device(device) if device is not None else bodies[0].sdf.phi.device
+    return torch.as_tensor(np.concatenate([b.row for b in bodies], axis=0), dtype=torch.float64, device=dev)
+
+
+def _mesh_volumes(rb, bodies):
+    rb = _bodies(rb)
+    bodies = list(bodies)
+    m = len(bodies)
+    if m > MAX_MESH_BODIES:
+        raise ValueError(f"{m} mesh bodies: at most {MAX_MESH_BODIES} per call")
+    if int(rb.shape[0]) != m:
+        raise ValueError(f"mesh_rb has {int(rb.shape[0])} rows for {m} mesh bodies")
+    vols, ext, org, sp = (ctypes.c_void_p * max(m, 1))(), [], [], []
+    for i, b in enumerate(bodies):
+        phi = T.dev(b.sdf.phi, "sdf.phi")
+        if phi.dtype != torch.float32 or phi.dim() != 3 or phi.device != rb.device:
+            raise ValueError("mesh body volume: expected a float32 (n0, n1, n2) tensor on mesh_rb's device")
+        vols[i] = phi.data_ptr()
+        ext += [int(v) for v in phi.shape]
+        org += T.as_f64_list(b.sdf.origin, 3)
+        sp.append(float(b.sdf.spacing))
+    return rb, m, (vols, _lib.i64x(ext or [0]), _lib.f64x(org or [0.0]), _lib.f64x(sp or [0.0]))
+
+
+def union_mesh_grid(mesh_rb, bodies, sd, vel, bound_min, cell_size, bias, rb_w=None):
+    """Unite the mesh bodies with the level set `sd` / `vel` already holds on a regular grid (`evaluate_grid`'s grid and
+    position rule): for every node and every body in turn, d = the body's volume sampled trilinearly at R^T (x - T) (outside
+    the volume: the sample at the clamped point plus the distance to the volume's box); d < sd -> sd = d and
+    vel = v + w x (x - T) where d <= 0, 0 where d > 0.  Analytic and mesh bodies compose by `evaluate_grid`, then this."""
+    rb, m, vol_args = _mesh_volumes(mesh_rb, bodies)
+    sd, vel = T.dev(sd, "sd"), T.dev(vel, "vel")
+    if sd.dim() != 3 or tuple(vel.shape) != tuple(sd.shape) + (3,):
+        raise ValueError(f"sd / vel: expected shapes (n0, ..) and (n0, .., 3) on a 3D grid, got {tuple(sd.shape)}, {tuple(vel.shape)}")
+    if rb_w is not None:
+        rb_w = T.dev(rb_w, "rb_w", (m, 3))
+        if rb_w.dtype != torch.float64:
+            raise TypeError("rb_w: expected float64")
+    lib = _lib.load()
+    f = lambda a: _lib.f64x(T.as_f64_list(a, 3))  # noqa: E731
+    _lib.check(lib.mfs_mesh_union_grid3d(T.ptr(rb), None if rb_w is None else T.ptr(rb_w), m, *vol_args,
+                                         _lib.i64x(tuple(int(v) for v in sd.shape)), f(bound_min), f(bias), f(cell_size),
+                                         T.ptr(sd), T.code(sd), T.ptr(vel), T.code(vel), T.stream()),
+               "mfs_mesh_union_grid3d")
+
+
+def project_mesh(mesh_rb, bodies, position):
+    """`project` for mesh bodies, in place: for every body in turn a particle whose sampled d < 0 moves by -d * n, n the
+    normalised gradient of the trilinear interpolant rotated to the world frame (central differences of samples one
+    spacing apart where it vanishes; still zero: the particle stays).  Particles with d >= 0 are not written."""
+    rb, m, vol_args = _mesh_volumes(mesh_rb, bodies)
+    position = T.dev(position, "position")
+    assert position.shape[-1] == 3
+    lib = _lib.load()
+    _lib.check(lib.mfs_mesh_project3d(T.ptr(rb), m, *vol_args, T.ptr(position), T.code(position),
+                                      int(position.numel() // 3), T.stream()), "mfs_mesh_project3d")
