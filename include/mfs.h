@@ -790,6 +790,32 @@ int mfs_mesh_project3d(const void* mesh_rb, int64_t num_bodies, const void* cons
                        const int64_t* extents_host, const double* origins_host, const double* spacings_host,
                        void* position, int pos_dt, int64_t num_positions, mfs_stream stream);
 
+/* ------------------------------------------------------------------------- */
+/* Liquid skin (csrc/mfs_skin.hip; DESIGN.md "Liquid skin")                    */
+/* ------------------------------------------------------------------------- */
+/* No reference counterpart: the reference plots points.  Additions: the ABI version stays.
+ * Zhu & Bridson's particle surface on a lattice (shape, origin, spacing as above: every extent >= 2, fewer than 2^31
+ * nodes, scalar spacing h).  With d_i = x_i - x, w_i = max(1 - |d_i|^2 / R^2, 0)^3 and W = sum w_i, a node x gets
+ * phi = | sum w_i d_i | / W - r where W > 0 and the background (float) (R - r) where W == 0; float32 out, fp32
+ * arithmetic on coordinates taken relative to the node's brick in fp64 first.  0 < r < R <= 4 h.
+ * One workgroup owns a brick of 4 x 8 x 8 nodes and gathers from bins: bin (c0, c1, c2) of the (nb0 + 2) x (nb1 + 2) x
+ * (nb2 + 2) bins (nb = ceil(shape / (4, 8, 8)), C order) holds the particles of brick (c0 - 1, c1 - 1, c2 - 1)'s cell,
+ * [origin + (c - 1) E h, origin + c E h) along each axis, E the brick's edge in nodes.
+ * _bricks3d / _bins3d: their numbers (0 for a bad shape).
+ * _keys3d: keys[p] (int32) = particle p's bin, or _bins3d(shape) when it lies outside every bin or is not finite.
+ * particles: num_particles x 3, float32 or float64 (p_dt), fewer than 2^31.
+ * _field3d: sorted_particles are the particles in ascending order of key; bin_starts: _bins3d(shape) + 1 int32, the
+ * index of the first particle with key >= b (so the last entry counts the binned ones; the rest are never read).  The
+ * caller's order inside a bin is the order of summation: a stable sort makes phi a function of the input alone.  No
+ * atomics.  survivors: null, or _bricks3d(shape) int32, the particles each brick's nodes looped over.              */
+int64_t mfs_skin_bricks3d(const int64_t shape[3]);
+int64_t mfs_skin_bins3d(const int64_t shape[3]);
+int mfs_skin_keys3d(const int64_t shape[3], const double origin[3], double spacing, const void* particles, int p_dt,
+                    int64_t num_particles, void* keys, mfs_stream stream);
+int mfs_skin_field3d(const int64_t shape[3], const double origin[3], double spacing, double radius, double influence,
+                     const void* sorted_particles, int p_dt, int64_t num_particles, const void* bin_starts, void* phi,
+                     void* survivors, mfs_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -236,6 +236,10 @@ SIGNATURES = {
     "mfs_meshsdf_sign3d": (_i, [_pi64, _pd, _d, _p, _i64, _p, _p, _p]),
     "mfs_mesh_union_grid3d": (_i, [_p, _p, _i64, C.POINTER(_p), _pi64, _pd, _pd, _pi64, _pd, _pd, _pd, _p, _i, _p, _i, _p]),
     "mfs_mesh_project3d": (_i, [_p, _i64, C.POINTER(_p), _pi64, _pd, _pd, _p, _i, _i64, _p]),
+    "mfs_skin_bricks3d": (_i64, [_pi64]),
+    "mfs_skin_bins3d": (_i64, [_pi64]),
+    "mfs_skin_keys3d": (_i, [_pi64, _pd, _d, _p, _i, _i64, _p, _p]),
+    "mfs_skin_field3d": (_i, [_pi64, _pd, _d, _d, _d, _p, _i, _i64, _p, _p, _p, _p]),
 }
 
 _lib = None

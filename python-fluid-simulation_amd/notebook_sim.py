@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 import notebook_kernels as K
+from mfs import skin as _skin
 from mfs import surface as _surface
 from mfs.motion import BodyKinematics
 from solver import sdf3D as sdf
@@ -154,6 +155,16 @@ class NotebookSimulation:
         ({solid_levelset.phi < 0} on the doubled grid, open where the solid leaves the bounds)."""
         return _surface.simulation_surface(self, which, 3, normals=normals)
 
+    def skin_field(self, clip=True, radius=None, influence=None):
+        """The liquid's skin as a field (`mfs.skin.SkinField`): Zhu & Bridson's surface of `particle.x` at particle
+        resolution, on the solid level set's lattice (spacing GDX / 2).  clip=True: max(phi, -solid_levelset.phi), float64."""
+        return _skin.simulation_skin_field(self, clip, radius, influence)
+
+    def skin(self, normals=False, clip=True, radius=None, influence=None):
+        """`skin_field` extracted: an `mfs.surface.Mesh`, closed against the lattice border.  `surface("liquid")` shows the
+        field the pressure solve sees (spheres of 0.88 GDX at cell centres); this shows the liquid."""
+        return _skin.extract(self.skin_field(clip, radius, influence), normals=normals)
+
     def step(self, duration_left=float("inf"), timings=None):
         """One pass of the loop body (ipynb:4571-4667, solver == 'apic').  Returns the dt it took."""
         p, g, sl, fl, fv = self.particle, self.grid, self.solid_levelset, self.fluid_levelset, self.fluid_volume
@@ -272,6 +283,9 @@ class SlabNotebookSimulation(NotebookSimulation):
 
     def surface(self, which="liquid", normals=False):
         raise NotImplementedError("surface() is single-GPU: gather the level set to one rank and call mfs.surface.isosurface")
+
+    def skin_field(self, clip=True, radius=None, influence=None):
+        raise NotImplementedError("skin() is single-GPU: gather the particles to one rank and call mfs.skin.field")
 
     def close(self):
         self.PressureSolver.close()

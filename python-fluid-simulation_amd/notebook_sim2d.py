@@ -95,6 +95,9 @@ class NotebookSimulation2D:
         ({solid_levelset.phi < 0} on the doubled grid): `NotebookSimulation.surface` one dimension down."""
         return _surface.simulation_surface(self, which, 2)
 
+    def skin(self, *args, **kw):
+        raise NotImplementedError("skin() is 3D (NotebookSimulation.skin, mfs.skin): the 2D class has `surface()`")
+
     def step(self, duration_left=float("inf"), timings=None):
         """One pass of the loop body.  Returns the dt it took."""
         p, g, sl, fl, fv = self.particle, self.grid, self.solid_levelset, self.fluid_levelset, self.fluid_volume
