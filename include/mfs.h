@@ -816,6 +816,38 @@ int mfs_skin_field3d(const int64_t shape[3], const double origin[3], double spac
                      const void* sorted_particles, int p_dt, int64_t num_particles, const void* bin_starts, void* phi,
                      void* survivors, mfs_stream stream);
 
+/* ------------------------------------------------------------------------- */
+/* Liquid seeding (csrc/mfs_seed.hip; DESIGN.md "Seeding liquid from shapes")  */
+/* ------------------------------------------------------------------------- */
+/* No reference counterpart: the reference fills boxes on the host.  Additions: the ABI version stays.
+ * Sites: shape[0] x shape[1] x shape[2] (each 1 .. 2^30), site (i,j,k) with the 64-bit index s = (i * n1 + j) * n2 + k.
+ * Its particle sits at x_a = origin_a + ((i_a + 0.5) + jitter * u_a) * spacing in float64, every operation rounded on its
+ * own, jitter in [0, 1], u_a = (h_a >> 8) * 2^-24 - 0.5 with, mix(x) being x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15,
+ * x *= 0x846ca68b, x ^= x >> 16 on uint32: h = mix(seed_lo), h = mix(h ^ seed_hi), h = mix(h ^ s_lo), h = mix(h ^ s_hi),
+ * h_a = mix(h + (a + 1) * 0x9E3779B9).
+ * Shapes: num_include >= 1 and num_exclude >= 0, at most 16 together, includes first.  The *_host arrays are HOST memory,
+ * read before the launch: volumes_host[i] the DEVICE pointer of shape i's volume, dtypes_host[i] its element type
+ * (MFS_F32 / MFS_F64), extents_host 3 int64 per shape (each >= 2, fewer than 2^31 nodes), origins_host 3 doubles,
+ * spacings_host one double, poses_host 12 doubles per shape: the rotation R row by row, then the translation T.  A
+ * shape's value at x is its volume sampled trilinearly in float64 at R^T (x - T), as mfs_mesh_union_grid3d samples;
+ * outside the volume: the sample at the clamped point plus the distance to its box.
+ * A site is kept iff (min over includes) < 0 and (min over excludes) > clearance, both strict; a NaN sample keeps nothing.
+ * One workgroup owns 256 consecutive sites; _blocks3d: their number (0 for a bad shape), at most 2^31 - 1 per call.
+ * _count3d: counts (int32 per workgroup; may be null) = the sites it keeps; masks (4 uint64 per workgroup; may be null;
+ * not both) = the ballots of its four waves, bit l of word w for site 256 b + 64 w + l.
+ * _fill3d: offsets (int64 per workgroup) = the exclusive scan of counts.  The kept sites' positions (pos_dt; float32 is
+ * the float64 value rounded once) go to rows offsets[b] + rank of `positions` (capacity x 3), rank counting the kept
+ * sites of the workgroup in ascending s, and s itself to `sites` (int64, may be null).  Rows >= capacity are not stored.
+ * No atomics: the output is in ascending s and two calls store the same bits.                                      */
+int64_t mfs_seed_blocks3d(const int64_t shape[3]);
+int mfs_seed_count3d(const int64_t shape[3], const double origin[3], double spacing, double jitter, uint64_t seed,
+                     int64_t num_include, int64_t num_exclude, const void* const* volumes_host, const int* dtypes_host,
+                     const int64_t* extents_host, const double* origins_host, const double* spacings_host,
+                     const double* poses_host, double clearance, void* counts, void* masks, mfs_stream stream);
+int mfs_seed_fill3d(const int64_t shape[3], const double origin[3], double spacing, double jitter, uint64_t seed,
+                    const void* masks, const void* offsets, void* positions, int pos_dt, void* sites, int64_t capacity,
+                    mfs_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -240,6 +240,10 @@ SIGNATURES = {
     "mfs_skin_bins3d": (_i64, [_pi64]),
     "mfs_skin_keys3d": (_i, [_pi64, _pd, _d, _p, _i, _i64, _p, _p]),
     "mfs_skin_field3d": (_i, [_pi64, _pd, _d, _d, _d, _p, _i, _i64, _p, _p, _p, _p]),
+    "mfs_seed_blocks3d": (_i64, [_pi64]),
+    "mfs_seed_count3d": (_i, [_pi64, _pd, _d, _d, C.c_uint64, _i64, _i64, C.POINTER(_p), _pint, _pi64, _pd, _pd, _pd, _d,
+                              _p, _p, _p]),
+    "mfs_seed_fill3d": (_i, [_pi64, _pd, _d, _d, C.c_uint64, _p, _p, _p, _i, _p, _i64, _p]),
 }
 
 _lib = None

@@ -437,3 +437,44 @@ def add_box(center, size, dx, rng, keep=None):
     if keep is not None:
         pos = pos[keep(pos)]
     return pos + rng.standard_normal(pos.shape) * dx * 0.3
+
+
+def solid_volume(gres, gdx, bound_min, rb_d=None, mesh_bodies=None, device="cuda"):
+    """The solid level set `NotebookSimulation.__init__` builds on the doubled grid (the analytic table of `rb_d`, then
+    `sdf.union_mesh_grid` for `mesh_bodies`) as a volume for `mfs.seed`: .phi float64 (2 * gres + 1), .origin
+    float64(float32(bound_min)), .spacing gdx / 2 -- the convention of `mfs.skin.simulation_skin_field`."""
+    dev = torch.device(device)
+    g = tuple(int(v) for v in gres)
+    bmin = np.asarray(bound_min, np.float32)
+    bsz = (np.asarray(g, np.float64) * gdx).astype(np.float32)
+    dres = tuple(2 * v + 1 for v in g)
+    dcs = bsz / (2 * np.asarray(g, np.int64))
+    bias = np.zeros(3, np.float32)
+    phi = torch.empty(dres, dtype=torch.float64, device=dev)
+    vel = torch.empty(dres + (3,), dtype=torch.float64, device=dev)
+    if rb_d is None:
+        rb_d = torch.zeros((0, 10, 4), dtype=torch.float64, device=dev)
+    sdf.evaluate_grid(rb_d, phi, vel, bmin, dcs, bias)
+    if mesh_bodies:
+        bodies = list(mesh_bodies)
+        if not all(isinstance(b, sdf.MeshBody) for b in bodies):
+            raise TypeError("mesh_bodies: expected a list of solver.sdf3D.MeshBody")
+        sdf.union_mesh_grid(sdf.mesh_rb(bodies, dev), bodies, phi, vel, bmin, dcs, bias)
+    return NS(phi=phi, origin=tuple(float(v) for v in bmin.astype(np.float64)), spacing=0.5 * float(gdx))
+
+
+def seed_particles(gres, gdx, bound_min, liquid, rb_d=None, mesh_bodies=None, clearance=0.0, jitter=1.0, seed=0,
+                   device="cuda"):
+    """Particles for `NotebookSimulation(gres, gdx, bound_min, rb_d, px, gdx / 2, mesh_bodies=...)` from any shape, made on
+    the GPU (`mfs.seed.fill`): the lattice of 2 * gres sites at spacing gdx / 2 (8 per cell) is filled where `liquid` -- an
+    `mfs.seed.Shape`, a `MeshBody`, a bare volume (`MeshSDF`, `SkinField`), or a list of them -- is negative and the
+    scene's solids are farther than `clearance`.  Returns px (P, 3) float64 on the volumes' device, in ascending site index.
+
+    The solids are `solid_volume`: the level set the constructor builds, wrapped as the single exclude volume with origin
+    float64(float32(bound_min)) and spacing gdx / 2.  That convention ignores that the solid lattice's per-axis cell size,
+    float32(gres * gdx) / (2 * gres), is float32-rounded, about 6e-8 relative: a particle within that of a solid's surface
+    may be judged the other way, and the step's own projection (`sdf.project`, `sdf.project_mesh`) owns what is left."""
+    from mfs import seed as _seed
+    solid = solid_volume(gres, gdx, bound_min, rb_d, mesh_bodies, device)
+    return _seed.fill(liquid, tuple(2 * int(v) for v in gres), solid.origin, solid.spacing, exclude=[solid],
+                      clearance=clearance, jitter=jitter, seed=seed)
