@@ -22,7 +22,10 @@
 //    traffic at all; the in-plane neighbours (y+-1 rows, z+-1 cells) come from an
 //    LDS-staged copy of the current plane tile (double buffered, one barrier per
 //    plane, LDS-only wait so global prefetches stay in flight across it).
-//    Operands of step x+1 are requested before step x is computed.
+//    A step requests what step x+1 needs, computes plane x from registers and LDS,
+//    publishes plane x+1, waits ONCE for its loads and only then stores: no load is
+//    issued and consumed inside the arithmetic (vmcnt retires in order -- one such
+//    load, waited for at its use, drains every prefetch issued before it).
 //  * XCD-aware order: blocks with equal blockIdx%8 share an XCD and its L2; each
 //    label takes a contiguous range of (x-chunk, tile) work so the y-halo rows a
 //    tile re-reads were just fetched by its neighbour tile on the same L2.
@@ -47,13 +50,15 @@ constexpr int kXcds = 8;
 // One z-vector of the stencil.  zl / zr = v just left / right of the vector,
 // czr = cz just right of it.  `first`/`last`: the vector holds the boundary cell
 // z=0 / z=Nz-1, which is neither computed nor stored (PressureCGSolver3D.py:55-57).
+// stencil_calc: the arithmetic and the d.q partial; stencil_put: the store.  The march puts its stores behind the wait for
+// the step's loads (vm_arrived below); everything else calls stencil_vec = both.
 template <typename T, int VEC>
-__device__ __forceinline__ void stencil_vec(T* __restrict__ out_ptr, vec_t<T, VEC> vc, vec_t<T, VEC> vxp,
-                                            vec_t<T, VEC> vxm, vec_t<T, VEC> vyp, vec_t<T, VEC> vym,
-                                            vec_t<T, VEC> dg, vec_t<T, VEC> cxp, vec_t<T, VEC> cxm,
-                                            vec_t<T, VEC> cyp, vec_t<T, VEC> cym, vec_t<T, VEC> czm, double zl,
-                                            double zr, double czr, bool first, bool last, bool active, double& acc,
-                                            vec_t<T, VEC> czm2) {   // czm2: weight of the -z tap (= czm unless ASYM)
+__device__ __forceinline__ vec_t<T, VEC> stencil_calc(vec_t<T, VEC> vc, vec_t<T, VEC> vxp,
+                                                      vec_t<T, VEC> vxm, vec_t<T, VEC> vyp, vec_t<T, VEC> vym,
+                                                      vec_t<T, VEC> dg, vec_t<T, VEC> cxp, vec_t<T, VEC> cxm,
+                                                      vec_t<T, VEC> cyp, vec_t<T, VEC> cym, vec_t<T, VEC> czm, double zl,
+                                                      double zr, double czr, bool first, bool last, bool active, double& acc,
+                                                      vec_t<T, VEC> czm2) {   // czm2: weight of the -z tap (= czm unless ASYM)
   vec_t<T, VEC> o;
 #ifdef MFS_APPLY_NATIVE_MATH   // experiment: arithmetic in the storage type
   typedef T C;
@@ -77,6 +82,11 @@ __device__ __forceinline__ void stencil_vec(T* __restrict__ out_ptr, vec_t<T, VE
     const bool bnd = (first && j == 0) || (last && j == VEC - 1);
     if (active && !bnd) acc += (double)vc[j] * (double)o[j];
   }
+  return o;
+}
+
+template <typename T, int VEC>
+__device__ __forceinline__ void stencil_put(T* __restrict__ out_ptr, vec_t<T, VEC> o, bool first, bool last, bool active) {
   if (!active) return;
   if (!first && !last) {
     vstore<T, VEC>(out_ptr, o);
@@ -88,6 +98,22 @@ __device__ __forceinline__ void stencil_vec(T* __restrict__ out_ptr, vec_t<T, VE
     }
   }
 }
+
+template <typename T, int VEC>
+__device__ __forceinline__ void stencil_vec(T* __restrict__ out_ptr, vec_t<T, VEC> vc, vec_t<T, VEC> vxp,
+                                            vec_t<T, VEC> vxm, vec_t<T, VEC> vyp, vec_t<T, VEC> vym,
+                                            vec_t<T, VEC> dg, vec_t<T, VEC> cxp, vec_t<T, VEC> cxm,
+                                            vec_t<T, VEC> cyp, vec_t<T, VEC> cym, vec_t<T, VEC> czm, double zl,
+                                            double zr, double czr, bool first, bool last, bool active, double& acc,
+                                            vec_t<T, VEC> czm2) {
+  stencil_put<T, VEC>(out_ptr, stencil_calc<T, VEC>(vc, vxp, vxm, vyp, vym, dg, cxp, cxm, cyp, cym, czm, zl, zr, czr, first,
+                                                    last, active, acc, czm2), first, last, active);
+}
+
+// No instruction: tells the compiler that `s` is read here, so its wait for the load that produces `s` (and, the counter
+// retiring in order, for every load issued before that one) is placed here and not further down.
+template <typename S>
+__device__ __forceinline__ void vm_arrived(S s) { asm volatile("" ::"v"(s)); }
 
 // planes [xb, xe) and, optionally, a second range [xb2, xe2) handled by the same launch
 // (the multi-GPU driver applies its two edge planes {1, L-2} in one launch)
@@ -282,9 +308,10 @@ struct VSrc {
 // PD = prefetch depth in planes for the operand vector and its halo rows (the long-latency streams):
 // their loads for plane x+1+PD are issued at step x and consumed PD steps later, which keeps PD
 // planes of v per wave in flight -- the march is latency-paced, so bytes in flight are what set its speed.
-// XDEF (with FUSE): the PREVIOUS iteration's solution update x += alpha d_old rides in this launch too -- each
-// vector is updated by the step that owns it, d_old re-read from cache -- so that the x/r update kernel only
-// touches r and q.  The march is latency-paced, extra streams are nearly free for it; same values as k_update_xr's.
+// XDEF (with FUSE, PD 1): the PREVIOUS iteration's solution update x += alpha d_old rides in this launch too, so that the
+// x/r update kernel only touches r and q.  The d_old it needs is the .b half of the march's own raw operand: x of plane
+// x+2 is requested beside that operand at step x and updated where the operand is consumed (the run's first two planes:
+// by the prologue, from wc.b / wp.b).  Each plane is updated once, by the run that owns it.  Same values as k_update_xr's.
 // BOOK (with FUSE, small grids): the launch also CLOSES the previous iteration -- every workgroup folds the r.r partials
 // of the preceding x/r update itself (block_total_of: same order, same value in every workgroup), takes the convergence
 // decision and beta from that, and workgroup 0 writes the bookkeeping (cg_book).  The update kernel then needs no
@@ -308,7 +335,7 @@ k_pcg_apply_march(const T* __restrict__ v, T* __restrict__ out, const T* __restr
                   const double* __restrict__ done_flag, const T* __restrict__ fr, const T* __restrict__ fd_old,
                   T* __restrict__ fd_new, const double* __restrict__ beta_ptr, const T* __restrict__ cz2,
                   T* __restrict__ xdef = nullptr, const double* __restrict__ alpha_ptr = nullptr, BookArgs bk = BookArgs{}) {
-  static_assert(!XDEF || FUSE, "the deferred x update rides on the fused direction update");
+  static_assert(!XDEF || (FUSE && PD == 1), "the deferred x update rides on the fused direction update, prefetch depth 1");
   static_assert(!LMASK || (COMP && FUSE && PD == 1), "lane-level masking: compressed, fused, prefetch depth 1");
   static_assert(!BOOK || FUSE, "closing the previous iteration rides on the fused direction update");
   static_assert(kApplyBlock == kBlock, "block_total_of is written for kBlock threads");
@@ -418,9 +445,22 @@ k_pcg_apply_march(const T* __restrict__ v, T* __restrict__ out, const T* __restr
     RawVec<T, VEC> wh = {};
     const bool h0 = LDS && tid < 2 * nzv;
     if (h0) wh = src.raw((int64_t)x0 * sx + (tid < nzv ? m0 - Nz + tid * VEC : m0 + tile_len + (tid - nzv) * VEC));
+    // the +z weight of a wave's last vector lives in the next wave's lane 0: one dword from memory, requested a step
+    // ahead of its use and carried (cze: plane x's; the prologue requests plane x0's with the rest of the batch)
+    const bool zedge = lane == 63 && !last;
+    T cze = (T)0;
+    if (zedge) cze = cz[base + VEC];
     if (BOOK && book_pending) {                      // uniform over the workgroup: its first march
       if (close_previous()) return;
     }
+    // XDEF: the run's first two planes have no earlier step to ride on -- their x vectors are requested here (BOOK: alpha_x
+    // is known from here on, and a stop has returned before any x traffic) and updated from wc.b / wp.b once the image
+    // is staged.  Plane x0+1 only if the run owns it; plane x0-1 belongs to another run.
+    const bool xu0 = XDEF && active && !(mask_on && cls_c == kClsDead);
+    const bool xu1 = XDEF && active && x0 + 1 < x1 && !(mask_on && cls_n == kClsDead);
+    vec_t<T, VEC> xa = {}, xb = {};
+    if (xu0) xa = vload_nt<T, VEC>(xdef + base);
+    if (xu1) xb = vload_nt<T, VEC>(xdef + base + sx);
     vec_t<T, VEC> vm = src.fin(wm), vc = src.fin(wc), vp = src.fin(wp);
     CoefVec<T, VEC> cc = coef_load<T, VEC, COMP, NT, true, ASYM>(diag, cx, cy, cz, base, sx, Nz, cls_c, cz2);
     if (!COMP) cc.cxm = vload<T, VEC>(cx + base);
@@ -437,6 +477,16 @@ k_pcg_apply_march(const T* __restrict__ v, T* __restrict__ out, const T* __restr
                        src.ld((int64_t)x0 * sx + (lo ? m0 - Nz + j * VEC : m0 + tile_len + j * VEC)));
       }
       MFS_LDS_BARRIER();
+    }
+    if (xu0) {
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) xa[j] = (T)((double)xa[j] + alpha_x * (double)wc.b[j]);
+      vstore_nt<T, VEC>(xdef + base, xa);
+    }
+    if (xu1) {
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) xb[j] = (T)((double)xb[j] + alpha_x * (double)wp.b[j]);
+      vstore_nt<T, VEC>(xdef + base + sx, xb);
     }
     // The two halo rows of a plane (Nz elements below the tile, Nz above) are 2 * nzv vectors: thread t
     // owns halo vector t (low row first, then the high row), so the halo prefetch costs ONE vector of
@@ -463,14 +513,17 @@ k_pcg_apply_march(const T* __restrict__ v, T* __restrict__ out, const T* __restr
       const int64_t nb = base + sx;                         // this vector in plane x+1
       // The last step re-requests its own plane (addresses stay valid, values unused):
       // unconditional loads keep the prefetch free of control flow, so the compiler
-      // waits for them where they are consumed (the rotation below), not here.
+      // waits for them where they are consumed (vm_arrived below), not here.
       const int64_t nn = more ? nb : base;                  // plane x+1 (or x again on the last step)
       const int64_t n2 = more ? nb + sx : nb;               // plane x+2 (or x+1 again)
       const bool dead_c = mask_on && cc.cls == kClsDead;    // this step's own vector
       RawVec<T, VEC> qn = {};                               // operand vector, plane x+1+PD (MASK: not for a dead vector)
       if (!(mask_on && cls_n2 == kClsDead)) qn = src.raw((int64_t)min(x + 1 + PD, x1) * sx + m);
-      vec_t<T, VEC> xo = {}, dxo = {};                      // XDEF: this step's own x vector and d_old (cache hit)
-      if (XDEF && !dead_c) { xo = vload_nt<T, VEC>(xdef + base); dxo = vload<T, VEC>(fd_old + base); }
+      // XDEF: the x vector of the same plane rides with qn, whose .b half is the d_old it needs.  Only a plane the run
+      // owns: the clamped re-request of plane x1 on the last steps updates nothing.
+      const bool xu = XDEF && active && x + 2 < x1 && !(mask_on && cls_n2 == kClsDead);
+      vec_t<T, VEC> xq = {};
+      if (xu) xq = vload_nt<T, VEC>(xdef + base + 2 * sx);
       // plane x+1's coefficients (class known since the previous step); class of plane x+2
       CoefVec<T, VEC> cn = coef_load<T, VEC, COMP, NT, false, ASYM>(diag, cx, cy, cz, nn, sx, Nz, more ? cls_n : cc.cls, cz2);
       cn.cxm = cc.cxp;                                      // cx[x+1] was this step's upper-face weight
@@ -478,6 +531,8 @@ k_pcg_apply_march(const T* __restrict__ v, T* __restrict__ out, const T* __restr
       if (COMP) cls_nn = MASK ? cls[((int64_t)min(x + 3, x1) * sx + m) / VEC] : cls[n2 / VEC];
       RawVec<T, VEC> hn = {};                               // this thread's halo vector of plane x+1+PD
       if (hact) hn = src.raw((int64_t)min(x + 1 + PD, x1) * sx + hg);
+      T czn = (T)0;                                         // plane x+1's edge weight
+      if (zedge) czn = cz[nn + VEC];
       // ---- in-plane neighbours of plane x
       vec_t<T, VEC> vym, vyp;
       double zl, zr;
@@ -495,16 +550,12 @@ k_pcg_apply_march(const T* __restrict__ v, T* __restrict__ out, const T* __restr
         zr = (double)((lane == 63 && !last) ? v[base + VEC] : r);
       }
       const T czs = __shfl_down(cc.czm[0], 1, 64);
-      const double czr = (double)((lane == 63 && !last) ? cz[base + VEC] : czs);
-      stencil_vec<T, VEC>(out + base, vc, vp, vm, vyp, vym, cc.dg, cc.cxp, cc.cxm, cc.cyp, cc.cym, cc.czm, zl, zr, czr,
-                          first, last, active && !dead_c, acc, cc.czm2);
-      if (FUSE && active && !dead_c) vstore<T, VEC>(fd_new + base, vc);   // d_new of this vector (its z-boundary cells are 0 + beta*0)
-      if (XDEF && active && !dead_c) {
+      const double czr = (double)(zedge ? cze : czs);
+      const vec_t<T, VEC> o = stencil_calc<T, VEC>(vc, vp, vm, vyp, vym, cc.dg, cc.cxp, cc.cxm, cc.cyp, cc.cym, cc.czm, zl, zr,
+                                                   czr, first, last, active && !dead_c, acc, cc.czm2);
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) xo[j] = (T)((double)xo[j] + alpha_x * (double)dxo[j]);
-        vstore_nt<T, VEC>(xdef + base, xo);
-      }
-      // ---- rotate; publish plane x+1 to the other LDS buffer
+      for (int j = 0; j < VEC; ++j) vm_arrived(o[j]);       // (the arithmetic stays ahead of the barrier and of the wait below)
+      // ---- publish plane x+1 to the other LDS buffer
       if (more) {
         if (LDS) {
           T* bn = smem + (cur ^ 1) * buf_elems;
@@ -518,7 +569,23 @@ k_pcg_apply_march(const T* __restrict__ v, T* __restrict__ out, const T* __restr
           }
           MFS_LDS_BARRIER();
         }
-        vm = vc; vc = vp; vp = src.fin(PD == 1 ? qn : Q[0]); cc = cn;
+      }
+      // The rotation below copies registers that this step's loads fill, so the step ends with a full wait either way.
+      // Taken here, ahead of the stores, it covers the loads alone (they have had the stencil to arrive in); taken at
+      // the copies it would cover the stores' acknowledgements too.
+      vm_arrived(qn.a[0]); vm_arrived(qn.b[0]); vm_arrived(xq[0]);
+      vm_arrived(cn.dg[0]); vm_arrived(cn.cxp[0]); vm_arrived(cn.cym[0]); vm_arrived(cn.cyp[0]); vm_arrived(cn.czm[0]);
+      vm_arrived(cn.czm2[0]); vm_arrived((int)cls_nn); vm_arrived(hn.a[0]); vm_arrived(hn.b[0]); vm_arrived(czn);
+      stencil_put<T, VEC>(out + base, o, first, last, active && !dead_c);
+      if (FUSE && active && !dead_c) vstore<T, VEC>(fd_new + base, vc);   // d_new of this vector (its z-boundary cells are 0 + beta*0)
+      // ---- x of plane x+2; rotate
+      if (more) {
+        if (xu) {                                           // on the arrival of its d_old
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) xq[j] = (T)((double)xq[j] + alpha_x * (double)qn.b[j]);
+          vstore_nt<T, VEC>(xdef + base + 2 * sx, xq);
+        }
+        vm = vc; vc = vp; vp = src.fin(PD == 1 ? qn : Q[0]); cc = cn; cze = czn;
         if (MASK) { cls_n = cls_n2; cls_n2 = cls_nn; } else cls_n = cls_nn;
 #pragma unroll
         for (int k = 0; k + 1 < PD - 1; ++k) Q[k] = Q[k + 1];
