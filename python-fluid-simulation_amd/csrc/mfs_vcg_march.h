@@ -273,12 +273,11 @@ __device__ __forceinline__ void vm_store(T* p, vec_t<T, VEC> o, bool first, bool
 }
 
 // LDS: a ring of kVmRing plane slots (planes x-1, x, x+1 being read, x+2 being written), each the three components'
-// images [Nz halo | tile | Nz halo]
+// images [Nz halo | tile | Nz halo].  One definition of the image size for the kernel and the host's resolver
+// (mfs_vcg_form.h: vmarch_su, vmarch_lds_bytes)
 constexpr int kVmRing = 4;
 template <int VEC, int BLOCK = kVmBlock>
-__host__ __device__ inline int vm_su(int Nz) { return 2 * Nz + BLOCK * VEC; }
-template <typename T, int VEC, int BLOCK = kVmBlock, int RING = kVmRing>
-__host__ __device__ inline size_t vm_lds_bytes(int Nz) { return (size_t)RING * 3 * vm_su<VEC, BLOCK>(Nz) * sizeof(T); }
+__host__ __device__ inline int vm_su(int Nz) { return vmarch_su(VEC, BLOCK, Nz); }
 
 #define MFS_VM_PIN() __builtin_amdgcn_sched_barrier(0)
 // nontemporal hints (template NT; the host turns them on when the launch's working set exceeds the Infinity Cache, as the

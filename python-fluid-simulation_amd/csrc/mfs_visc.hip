@@ -11,15 +11,22 @@
 //  * k_visc_row_direct: straight from the caller's doubled-grid `sphi` / `vol`
 //    arrays (stride-2 reads).  Used for the module-level drop-ins `matvecmul` /
 //    `initialize_solver` and once per solve for the RHS.
-//  * k_vcg_apply: the per-iteration kernel.  Once per solve k_vcg_setup
+//  * the compact form of the CG engine.  Once per solve k_vcg_setup
 //    de-interleaves `vol` into its 7 used parity classes (cell centres, 3 face
 //    classes, 3 edge classes) and `sphi >= 0` at the 3 face
 //    classes into byte masks, all unit-stride.  A tap's mask sample is always the
 //    validity of the tapped face itself, so the masks are per-DOF bytes.
 //    Algorithmic traffic: 3 (v) + 7 (vol classes) + 3 (out) scalars + 3 mask bytes
 //    per cell, vs 8x-strided reads of two (2N+1)^3 arrays in the reference.
+//    Its kernels: k_vcg_apply_march (mfs_vcg_march.h), the per-iteration kernel
+//    on rows of whole vectors; k_vcg_apply_all, one cell per lane, for the masked
+//    initial q = A x, the stand-alone apply and every grid the march cannot
+//    serve; k_vcg_apply_row on degenerate grids; k_vcg_resident
+//    (mfs_vcg_resident.h), the whole loop of a small grid in one launch.
+//    Which one a launch takes, and which loop runs, is decided in mfs_vcg_form.h.
 #include "mfs_cg_core.h"
 #include "mfs_p2p.h"
+#include "mfs_vcg_form.h"
 
 // workgroup barrier that waits on LDS traffic only: the global prefetch of the next plane stays in flight
 #define MFS_VISC_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
@@ -427,7 +434,7 @@ struct Box3 { int lo[3], hi[3]; };   // face-index box [lo, hi) of one row
 // row's operands: S::vol(p, ox, oy, oz) = volume class p at compact index (x+ox, y+oy, z+oz),
 // S::vel(comp, dx, dy, dz) = velocity component at face (x+dx, y+dy, z+dz), S::tap_ok(...) = validity of
 // that face.  The global sampler reads the arrays directly (every load unconditional, so the ~40 loads of
-// a face are in flight together); the LDS sampler of the tiled kernel reads the staged plane tiles.
+// a face are in flight together); the samplers of the marching and resident kernels read registers and LDS.
 // MASK=false drops the tap masks: in the CG the operand is `d`, which is exactly 0 on solid and
 // array-boundary faces, so they cannot matter; the initial q = A x (x = extrapolated velocity, non-zero
 // on solid faces) and the stand-alone apply use MASK=true.  The row's OWN mask (solid face -> out = 0)
@@ -440,7 +447,7 @@ template <int AXIS, bool MASK, int NC, typename S>
 __device__ __forceinline__ void vcg_row_n(const S& smp, double k1, double k2, const bool (&own_ok)[NC], double (&out)[NC],
                                           double (&own_out)[NC]) {
   // The arithmetic is spelled out -- contraction off, fused multiply-adds written where they are wanted -- so that
-  // every kernel built on this function (one cell per lane, LDS tiles, x-marching vectors, boundary slabs) rounds
+  // every kernel built on this function (one cell per lane, x-marching vectors, boundary slabs, resident boxes) rounds
   // identically whatever else the compiler finds around the call: where `(diag * own) - (k vol) * nb` may fuse
   // either product into the subtraction, two kernels used to differ in the last bit.
 #pragma clang fp contract(off)
@@ -561,8 +568,7 @@ __global__ void __launch_bounds__(256) k_vcg_diag(Compact c, double k1, T* __res
   out[i] = (T)dg;
 }
 
-// rows of ONE component over a box of faces (used for the three boundary slabs the
-// fused kernel does not cover, and as the simple reference form)
+// rows of ONE component over a box of faces (the boundary slabs of degenerate grids, one launch each)
 template <typename T, int AXIS, bool MASK>
 __global__ void __launch_bounds__(256)
 k_vcg_apply_row(Compact c, double k1, double k2, Vec3T<T> v, T* __restrict__ out, Box3 bx, double* __restrict__ partial,
@@ -655,73 +661,16 @@ __device__ __forceinline__ double vcg_slab_rows_fused(const Compact& c, double k
   return acc;
 }
 
-template <typename T, bool MASK>
-__global__ void __launch_bounds__(256)
-k_vcg_apply_slabs(Compact c, double k1, double k2, Vec3T<T> v, T* __restrict__ ox, T* __restrict__ oy, T* __restrict__ oz,
-                  Box3 b0, Box3 b1, Box3 b2, int g0, int g1, double* __restrict__ partial,
-                  const double* __restrict__ done_flag) {
-  if (done_flag && *done_flag != 0.0) return;
-  const int b = blockIdx.x, g2 = gridDim.x - g0 - g1;
-  double acc;
-  if (b < g0) acc = vcg_slab_rows<T, 0, MASK>(c, k1, k2, v, ox, b0, b, g0);
-  else if (b < g0 + g1) acc = vcg_slab_rows<T, 1, MASK>(c, k1, k2, v, oy, b1, b - g0, g1);
-  else acc = vcg_slab_rows<T, 2, MASK>(c, k1, k2, v, oz, b2, b - g0 - g1, g2);
-  const double tot = block_sum<256>(acc);
-  if (threadIdx.x == 0) partial[blockIdx.x] = tot;
-}
-
-// XCD-aware block order: workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share an XCD and
-// its L2), so neighbouring tiles -- which read each other's halo rows -- would sit on different L2s and every
-// halo line would be fetched from HBM twice.  Give each XCD a CONTIGUOUS range of logical tile ids instead.
-__device__ __forceinline__ int xcd_logical_block(int on) {
-  if (!on) return blockIdx.x;
-  const int G = gridDim.x, nch = min(G, 8);
-  const int xcd = blockIdx.x % nch, slot = blockIdx.x / nch;
-  const int per = G / nch, extra = G - per * nch;           // the first `extra` XCDs own one more block
-  return xcd * per + min(xcd, extra) + slot;
-}
-
-// The per-iteration kernel: all three rows of cell (x,y,z) by one thread, over the
-// box x in [1,Nx-2], y in [1,Ny-2], z in [1,Nz-2] where every row is an interior
-// face.  The three rows share most of their operands (27 distinct velocity and 16
-// distinct volume samples instead of 45 + 21); written from the one tap table, the
-// duplicates are merged by the compiler (all inputs are read-only __restrict__).
-// Lanes run along z (coalesced rows), 4 rows of y per workgroup, marching over a
-// chunk of x planes so the x-1 / x+1 operands are L1/L2 hits of the previous step.
-template <typename T, bool MASK>
-__global__ void __launch_bounds__(256)
-k_vcg_apply_fused(Compact c, double k1, double k2, Vec3T<T> v, T* __restrict__ ox, T* __restrict__ oy,
-                  T* __restrict__ oz, int xchunk, int nbz, int nby, int xcd_order, double* __restrict__ partial,
-                  const double* __restrict__ done_flag) {
-  if (done_flag && *done_flag != 0.0) return;
-  const int Nx = c.N[0], Ny = c.N[1], Nz = c.N[2];
-  const int lb = xcd_logical_block(xcd_order);
-  const int bz = lb % nbz, by = (lb / nbz) % nby, bxk = lb / (nbz * nby);
-  const int zr = 1 + bz * 64 + (threadIdx.x & 63), yr = 1 + by * 4 + (threadIdx.x >> 6);
-  const bool active = zr <= Nz - 2 && yr <= Ny - 2;
-  const int z = min(zr, Nz - 2), y = min(yr, Ny - 2);      // inactive lanes recompute a valid cell, store nothing
-  const int x0 = 1 + bxk * xchunk, x1 = min(x0 + xchunk, Nx - 1);
-  double acc = 0.0;
-  for (int x = x0; x < x1; ++x) {
-    double o0, o1, o2;
-    const double r0 = vcg_row<T, 0, MASK>(c, k1, k2, v, x, y, z, o0);
-    const double r1 = vcg_row<T, 1, MASK>(c, k1, k2, v, x, y, z, o1);
-    const double r2 = vcg_row<T, 2, MASK>(c, k1, k2, v, x, y, z, o2);
-    if (active) {
-      const T t0 = (T)r0, t1 = (T)r1, t2 = (T)r2;
-      ox[((int64_t)x * Ny + y) * Nz + z] = t0;
-      oy[((int64_t)x * (Ny + 1) + y) * Nz + z] = t1;
-      oz[((int64_t)x * Ny + y) * (Nz + 1) + z] = t2;
-      acc += o0 * (double)t0 + o1 * (double)t1 + o2 * (double)t2;
-    }
-  }
-  const double tot = block_sum<256>(acc);
-  if (threadIdx.x == 0) partial[blockIdx.x] = tot;
-}
-
-// The fused box AND the three boundary slabs in one launch (one kernel boundary less per CG iteration -- what counts on
-// launch-bound grids): blocks [0, gmain) are k_vcg_apply_fused's, the rest k_vcg_apply_slabs'; same block -> partial-sum
-// slot mapping as the two launches, so the dot product is bit-identical.
+// One cell per lane.  Blocks [0, gmain): all three rows of cell (x,y,z) by one thread, over the box x in [1,Nx-2],
+// y in [1,Ny-2], z in [1,Nz-2] where every row is an interior face.  The three rows share most of their operands (27
+// distinct velocity and 16 distinct volume samples instead of 45 + 21); written from the one tap table, the duplicates
+// are merged by the compiler (all inputs are read-only __restrict__).  Lanes run along z (coalesced rows), 4 rows of y
+// per workgroup, marching over a chunk of x planes so the x-1 / x+1 operands are L1/L2 hits of the previous step.
+// XCD-aware block order (xcd_order): workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share an XCD and
+// its L2), so neighbouring tiles -- which read each other's halo rows -- would sit on different L2s and every halo line
+// would be fetched from HBM twice; each XCD gets a CONTIGUOUS range of logical tile ids instead.
+// The remaining blocks: the three boundary slabs (u at x = Nx-1, v at y = Ny-1, w at z = Nz-1) -- blocks [0, g0) of them
+// take the first box, [g0, g0+g1) the second, the rest the third.
 template <typename T, bool MASK>
 __global__ void __launch_bounds__(256)
 k_vcg_apply_all(Compact c, double k1, double k2, Vec3T<T> v, T* __restrict__ ox, T* __restrict__ oy, T* __restrict__ oz,
@@ -764,135 +713,6 @@ k_vcg_apply_all(Compact c, double k1, double k2, Vec3T<T> v, T* __restrict__ ox,
   if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
-// The per-iteration kernel, LDS-staged: a workgroup owns a TY x TZ tile of cells and marches over a
-// chunk of x planes.  The ten operand arrays of the operator (3 velocity components, 7 volume classes)
-// are staged plane by plane into LDS as (TY+2) x (TZ+2) tiles -- one ring of three planes (x-1, x, x+1)
-// per array -- with coalesced row-segment loads issued one plane ahead into registers; every one of the
-// 43 samples a cell's three rows need is then an LDS read at a constant offset.  Global traffic per cell
-// drops from 43 L2-served loads (the vector L1 cannot hold the working set of 12 waves) to the 10 streams
-// plus halo.  Arithmetic, operand order and results are those of k_vcg_apply_fused (same vcg_row_s).
-template <typename T, int TY, int TZ>
-struct VTile {
-  static constexpr int PY = TY + 2, PZ = TZ + 2, PLANE = PY * PZ, NARR = 10, BLOCK = TY * TZ;
-  static constexpr int NSTG = (PLANE + BLOCK - 1) / BLOCK;          // staging elements per thread per array
-  static constexpr size_t lds_bytes() { return (size_t)NARR * 3 * PLANE * sizeof(T); }
-};
-
-template <typename T, int TY, int TZ>
-struct LdsSampler {
-  typedef VTile<T, TY, TZ> V;
-  const T* base;          // smem + this thread's centre (ty + 1, tz + 1)
-  int slot[3];            // element offsets of the ring slots holding planes x-1, x, x+1
-  // array ids: 0..2 velocity components, 2 + p volume class p (1..7)
-  __device__ __forceinline__ double at(int arr, int ox, int oy, int oz) const {
-    return (double)base[arr * 3 * V::PLANE + slot[ox + 1] + oy * V::PZ + oz];
-  }
-  __device__ __forceinline__ double vol(int p, int ox, int oy, int oz) const { return at(2 + p, ox, oy, oz); }
-  __device__ __forceinline__ double vel(int comp, int dx, int dy, int dz) const { return at(comp, dx, dy, dz); }
-  __device__ __forceinline__ bool tap_ok(int, int, int, int) const { return true; }
-};
-
-template <typename T, int TY, int TZ>
-__global__ void __launch_bounds__(TY * TZ)
-k_vcg_apply_tiled(Compact c, double k1, double k2, Vec3T<T> v, T* __restrict__ ox, T* __restrict__ oy,
-                  T* __restrict__ oz, int xchunk, int nbz, int nby, int xcd_order, double* __restrict__ partial,
-                  const double* __restrict__ done_flag) {
-  typedef VTile<T, TY, TZ> V;
-  if (done_flag && *done_flag != 0.0) return;
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  T* const smem = reinterpret_cast<T*>(smem_raw);
-  const int Nx = c.N[0], Ny = c.N[1], Nz = c.N[2];
-  const int tid = threadIdx.x;
-  const int lb = xcd_logical_block(xcd_order);
-  const int bz = lb % nbz, by = (lb / nbz) % nby, bxk = lb / (nbz * nby);
-  const int y0 = 1 + by * TY, z0 = 1 + bz * TZ;               // first cell of the tile
-  const int ty = tid / TZ, tz = tid - ty * TZ;
-  const int yr = y0 + ty, zr = z0 + tz;
-  const bool active = zr <= Nz - 2 && yr <= Ny - 2;
-  const int y = min(yr, Ny - 2), z = min(zr, Nz - 2);          // mask / store addresses of inactive lanes stay valid
-  const int x0 = 1 + bxk * xchunk, x1 = min(x0 + xchunk, Nx - 1);
-  // the ten arrays: base pointer, rows per plane, row length
-  const T* ap[V::NARR];
-  int d1[V::NARR], d2[V::NARR];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { ap[a] = v.p[a]; d1[a] = Ny + (a == 1); d2[a] = Nz + (a == 2); }
-  int q1[V::NARR], q2[V::NARR];                               // storage pitches (rows per plane, elements per row)
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { q1[a] = d1[a]; q2[a] = d2[a]; }
-#pragma unroll
-  for (int p = 1; p < 8; ++p) {
-    ap[2 + p] = (const T*)c.vol[p]; d1[2 + p] = c.dim(p, 1); d2[2 + p] = c.dim(p, 2); q1[2 + p] = c.py; q2[2 + p] = c.pz;
-  }
-  // staging slots of this thread: tile element e = tid + k * BLOCK  <->  (y0 - 1 + e / PZ, z0 - 1 + e % PZ)
-  int se[V::NSTG], sgy[V::NSTG], sgz[V::NSTG];
-#pragma unroll
-  for (int k = 0; k < V::NSTG; ++k) {
-    se[k] = tid + k * V::BLOCK;
-    const int ly = se[k] / V::PZ;
-    sgy[k] = y0 - 1 + ly;
-    sgz[k] = z0 - 1 + (se[k] - ly * V::PZ);
-  }
-  T stg[V::NARR][V::NSTG];
-  auto stage_load = [&](int X) {
-#pragma unroll
-    for (int a = 0; a < V::NARR; ++a) {
-#pragma unroll
-      for (int k = 0; k < V::NSTG; ++k) {
-        const bool ok = se[k] < V::PLANE && sgy[k] < d1[a] && sgz[k] < d2[a];
-        // clamped address, unconditional load: the prefetch stays free of control flow
-        const int gy = min(sgy[k], d1[a] - 1), gz = min(sgz[k], d2[a] - 1);
-        const T val = ap[a][((int64_t)X * q1[a] + gy) * q2[a] + gz];
-        stg[a][k] = ok ? val : (T)0;
-      }
-    }
-  };
-  auto stage_store = [&](int slot_off) {
-#pragma unroll
-    for (int a = 0; a < V::NARR; ++a) {
-#pragma unroll
-      for (int k = 0; k < V::NSTG; ++k)
-        if (se[k] < V::PLANE) smem[a * 3 * V::PLANE + slot_off + se[k]] = stg[a][k];
-    }
-  };
-  LdsSampler<T, TY, TZ> smp;
-  smp.base = smem + (ty + 1) * V::PZ + tz + 1;
-  smp.slot[0] = 0; smp.slot[1] = V::PLANE; smp.slot[2] = 2 * V::PLANE;
-  // prologue: planes x0-1, x0, x0+1
-  stage_load(x0 - 1); stage_store(smp.slot[0]);
-  stage_load(x0);     stage_store(smp.slot[1]);
-  stage_load(x0 + 1); stage_store(smp.slot[2]);
-  MFS_VISC_LDS_BARRIER();
-  double acc = 0.0;
-  for (int x = x0; x < x1; ++x) {
-    const bool more = x + 1 < x1;
-    if (more) stage_load(x + 2);                               // in flight while this plane is computed
-    const int64_t f0 = ((int64_t)x * Ny + y) * Nz + z, f1 = ((int64_t)x * (Ny + 1) + y) * Nz + z,
-                  f2 = ((int64_t)x * Ny + y) * (Nz + 1) + z;
-    const unsigned fm = c.msk[c.idx(x, y, z)];
-    const bool ok0 = (fm & 1) != 0, ok1 = (fm & 2) != 0, ok2 = (fm & 4) != 0;
-    double o0, o1, o2;
-    const double r0 = vcg_row_s<0, false>(smp, k1, k2, ok0, o0);
-    const double r1 = vcg_row_s<1, false>(smp, k1, k2, ok1, o1);
-    const double r2 = vcg_row_s<2, false>(smp, k1, k2, ok2, o2);
-    if (active) {
-      const T t0 = (T)r0, t1 = (T)r1, t2 = (T)r2;
-      ox[f0] = t0;
-      oy[f1] = t1;
-      oz[f2] = t2;
-      acc += o0 * (double)t0 + o1 * (double)t1 + o2 * (double)t2;
-    }
-    if (more) {
-      MFS_VISC_LDS_BARRIER();                                  // everyone is done with plane x-1's slot
-      stage_store(smp.slot[0]);                                // ... which now receives plane x+2
-      MFS_VISC_LDS_BARRIER();
-      const int s0 = smp.slot[0];
-      smp.slot[0] = smp.slot[1]; smp.slot[1] = smp.slot[2]; smp.slot[2] = s0;
-    }
-  }
-  const double tot = block_sum<V::BLOCK>(acc);
-  if (threadIdx.x == 0) partial[blockIdx.x] = tot;
-}
-
 }  // namespace mfs
 
 #include "mfs_vcg_march.h"
@@ -911,19 +731,16 @@ struct mfs_vcg3d {
   double k1, k2;
   bool is_setup;
   int grid_row;
-  int mask_cg;   // 1: keep the tap masks in CG applies too (debug / A-B)
-  int tiled;     // 1: CG applies use the LDS-staged kernel (default); 0: the direct-load fused kernel
-  int xchunk_tiled;
   int xcd_order;   // 1 / 0: XCD-contiguous tile order on / off; -1 auto
   int split_x;     // 1: the x update rides in the direction-update kernel (default)
   int skip_top_x;  // slab decomposition: the u row at x = Nx-1 belongs to the right neighbour (a ghost here)
-  int merge_slabs; // 1 / 0: the fused box and the boundary slabs in one launch (default) / two
   int march;       // 1 (default): CG applies run the x-marching vector kernel (mfs_vcg_march.h) where the grid allows it
   int march_bpc;   // its workgroups per CU (2: what its register budget makes resident)
-  int march_vec;   // experiment: 2 = 8-byte vectors for fp32 state
-  mfs_p2p* p2p;    // window transport of the slab loop (mfs_vcg3d_attach_p2p); null: the caller moves halos / scalars
+  int march_block; // MFS_VISC_MARCH_BLOCK: 256 / 512 / 5123 force its geometry (A/B), 0 auto; read at creation
+  mfs_p2p* p2p;   // window transport of the slab loop (mfs_vcg3d_attach_p2p); null: the caller moves halos / scalars
   int64_t last_iters;   // iterations of this engine's previous converged solve (sizes the first batch of the next one)
   int jacobi;      // 1: opt-in Jacobi-preconditioned loop (mfs_vcg3d_set_jacobi; NOT the reference's iteration)
+  int jacobi_z;    // MFS_VISC_JACOBI_Z: its stored-z form 0 / 1, -1 auto by size; read at creation
   void* diag;      // its diagonal (n elements, built by setup when the flag is on)
   double* part_rz; // its r.z partials
   bool diag_ready;
@@ -1000,7 +817,7 @@ static int launch_rows_direct(const int64_t gres[3], double scale, double mu, co
   return MFS_OK;
 }
 
-// the three slabs of interior faces outside the fused box: u at x = Nx-1, v at y = Ny-1, w at z = Nz-1
+// the three slabs of interior faces outside the box where all three rows are interior: u at x = Nx-1, v at y = Ny-1, w at z = Nz-1
 static Box3 vslab_box(const mfs_vcg3d* h, int ax) {
   Box3 b;
   for (int a = 0; a < 3; ++a) { b.lo[a] = 1; b.hi[a] = h->g.sh(ax, a) - 1; }
@@ -1013,77 +830,28 @@ static int vslab_grid(const Box3& b) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(256, (n + 255) / 256));
 }
 
-// can the x-marching vector kernel serve this engine / these operands?  (rows of whole 16-byte vectors, 16-byte aligned
-// vectors, one halo vector per thread, the ring of plane buffers within the CU's LDS: two workgroups per CU up to 80 KB
-// each, one beyond that -- measured at 256^3 fp32: one workgroup per CU runs within 7 % of two, the kernel is paced
-// by its instruction stream, not by occupancy)
-constexpr size_t kVmMaxLds = 152 * 1024;
-// geometry of the march for this engine: threads per workgroup (= z-vectors per tile) * 10 + ring slots; 0: rows too long.
-// 256 x 4 wherever two such workgroups share a CU; 512 x 4 where only one 256-vector workgroup would fit anyway (fp64 from
-// Nz ~ 150, fp32 from Nz ~ 300); 512 x 3 (a second barrier per plane) where even that ring exceeds the LDS (fp64 380 < Nz <= 512)
-template <typename T, int VEC>
-static int vcg_march_geom(const mfs_vcg3d* h) {
-  const int Nz = h->g.N[2], nzv2 = 2 * (Nz / VEC);
-  const int knob = env_int("MFS_VISC_MARCH_BLOCK", 0);          // A/B: 256 / 512 / 5123 force, 0 auto
-  const bool f2564 = nzv2 <= 256 && vm_lds_bytes<T, VEC, 256, 4>(Nz) <= kVmMaxLds;
-  const bool f5124 = nzv2 <= 512 && vm_lds_bytes<T, VEC, 512, 4>(Nz) <= kVmMaxLds;
-  const bool f5123 = nzv2 <= 512 && vm_lds_bytes<T, VEC, 512, 3>(Nz) <= kVmMaxLds;
-  if (knob == 256 && f2564) return 2564;
-  if (knob == 512 && f5124) return 5124;
-  if (knob == 5123 && f5123) return 5123;
-  if (f2564 && vm_lds_bytes<T, VEC, 256, 4>(Nz) <= 80 * 1024) return 2564;
-  if (f5124) return 5124;
-  if (f2564) return 2564;
-  if (f5123) return 5123;
-  return 0;
-}
+// f(T{}) with the engine's element type
+template <class F>
+static auto vcg_typed(const mfs_vcg3d* h, F&& f) { return h->dt == MFS_F32 ? f(float{}) : f(double{}); }
 
-template <typename T, int VEC = VecOf<T>::N>
-static bool vcg_march_ok(const mfs_vcg3d* h, const void* v, const void* out) {
-  const int Nx = h->g.N[0], Ny = h->g.N[1], Nz = h->g.N[2];
-  if (!h->march || Nx < 3 || Ny < 3 || Nz % VEC != 0 || Nz < 2 * VEC) return false;
-  if (vcg_march_geom<T, VEC>(h) == 0) return false;
-  if (((uintptr_t)v % 16) != 0 || ((uintptr_t)out % 16) != 0) return false;
-  if ((int64_t)(Ny + 1) * (Nz + 4) > (int64_t)0x7fffffff / 2) return false;     // 32-bit in-plane offsets
-  return true;
-}
-
-template <typename T, int VEC, int WAVES, int NT, bool FUSE = false, int BLOCK = kVmBlock, int RING = kVmRing, bool COMP = false>
-static int vcg_march_launch_blk(mfs_vcg3d* h, const Vec3T<T>& vv, T* ob, double* partial, const double* done, hipStream_t st,
-                                int* nparts, const VmFuse<T>* fz) {
-  const int Nx = h->g.N[0], Ny = h->g.N[1], Nz = h->g.N[2];
-  const int ipp = (Ny - 2) * (Nz / VEC), tiles = (ipp + BLOCK - 1) / BLOCK;
-  const int64_t total = (int64_t)tiles * (Nx - 2);
-  const size_t lds = vm_lds_bytes<T, VEC, BLOCK, RING>(Nz);
-  const int bpc = lds > 80 * 1024 ? 1 : h->march_bpc;
-  const int gmain = (int)std::max<int64_t>(1, std::min<int64_t>(total, (int64_t)h->c.cus * bpc));
-  const Box3 b0 = vslab_box(h, 0), b1 = vslab_box(h, 1), b2 = vslab_box(h, 2);
-  const int g0 = h->skip_top_x ? 0 : vslab_grid(b0), g1 = vslab_grid(b1), g2 = vslab_grid(b2);
-  static bool attr_set = false;        // per instantiation: more than the default 64 KB of dynamic LDS
-  if (!attr_set) {
-    MFS_HIP_TRY(hipFuncSetAttribute((const void*)k_vcg_apply_march<T, VEC, WAVES, NT, FUSE, BLOCK, RING, COMP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)kVmMaxLds));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((k_vcg_apply_march<T, VEC, WAVES, NT, FUSE, BLOCK, RING, COMP>), dim3(gmain + g0 + g1 + g2), dim3(BLOCK), lds, st, h->cp, h->k1,
-                     h->k2, vv, ob + h->off[0], ob + h->off[1], ob + h->off[2], gmain, b0, b1, b2, g0, g1, partial, done,
-                     fz ? *fz : VmFuse<T>{});
-  MFS_LAUNCH_CHECK();
-  *nparts = gmain + g0 + g1 + g2;
-  return MFS_OK;
-}
-
-template <typename T, int VEC, int WAVES, int NT, bool FUSE = false, bool COMP = false>
-static int vcg_march_launch_nt(mfs_vcg3d* h, const Vec3T<T>& vv, T* ob, double* partial, const double* done, hipStream_t st,
-                               int* nparts, const VmFuse<T>* fz = nullptr) {
-  if constexpr (VEC == VecOf<T>::N && WAVES == MFS_VMARCH_MIN_WAVES) {
-    const int geom = vcg_march_geom<T, VEC>(h);
-    if (geom == 5124) return vcg_march_launch_blk<T, VEC, WAVES, NT, FUSE, 512, 4, COMP>(h, vv, ob, partial, done, st, nparts, fz);
-    if constexpr (!FUSE) {
-      if (geom == 5123) return vcg_march_launch_blk<T, VEC, WAVES, NT, FUSE, 512, 3, COMP>(h, vv, ob, partial, done, st, nparts, fz);
-    }
-  }
-  return vcg_march_launch_blk<T, VEC, WAVES, NT, FUSE, 256, 4, COMP>(h, vv, ob, partial, done, st, nparts, fz);
+// The form of one stencil launch out = A v on this engine.  mfs_vcg_form.h decides; nothing in this file recomputes the
+// march's geometry, LDS bytes or grid.  masked = false only for operands that are 0 on solid / array-boundary faces (the
+// CG's d); fused: the caller asks for the march that forms d_j = r + beta d_{j-1} and updates x on the way.
+// (Two workgroups per CU up to 80 KB of LDS each, one beyond that -- measured at 256^3 fp32: one workgroup per CU runs
+// within 7 % of two, the kernel is paced by its instruction stream, not by occupancy.)
+static VMarchForm vcg_form(const mfs_vcg3d* h, const void* v, const void* out, bool masked, bool fused) {
+  VMarchInputs in{};
+  in.elt = dtype_size(h->dt);
+  in.Nx = h->g.N[0]; in.Ny = h->g.N[1]; in.Nz = h->g.N[2];
+  in.march = h->march; in.block_knob = h->march_block; in.march_bpc = h->march_bpc; in.compress = h->compress;
+  in.march_nt = h->march_nt;
+  in.tw_block = h->cp.tw_block;
+  in.aligned = ((uintptr_t)v % 16) == 0 && ((uintptr_t)out % 16) == 0;
+  in.masked = masked; in.fused = fused;
+  in.cus = h->c.cus;
+  VMarchForm f;
+  vmarch_form(in, &f);
+  return f;
 }
 
 // ---- live chunks of the flat CG vectors (mfs_cg_core.h LiveMap): a face is DEAD when its operator row is empty -- an
@@ -1129,10 +897,10 @@ static int vcg_build_live(mfs_vcg3d* h, hipStream_t st) {
   int* count = list + nchunks;
   MFS_HIP_TRY(hipMemsetAsync(flags, 0, (size_t)nchunks * sizeof(int), st));
   const int64_t nvec = (h->n + vec - 1) / vec;
-  if (h->dt == MFS_F32)
-    hipLaunchKernelGGL((k_vcg_live_flags<float, 4>), dim3(cdiv(nvec, 256)), dim3(256), 0, st, h->cp, (const float*)h->c.r, (const float*)h->c.d, h->n, h->off[1], h->off[2], flags);
-  else
-    hipLaunchKernelGGL((k_vcg_live_flags<double, 2>), dim3(cdiv(nvec, 256)), dim3(256), 0, st, h->cp, (const double*)h->c.r, (const double*)h->c.d, h->n, h->off[1], h->off[2], flags);
+  vcg_typed(h, [&](auto t) {
+    typedef decltype(t) T;
+    hipLaunchKernelGGL((k_vcg_live_flags<T, VecOf<T>::N>), dim3(cdiv(nvec, 256)), dim3(256), 0, st, h->cp, (const T*)h->c.r, (const T*)h->c.d, h->n, h->off[1], h->off[2], flags);
+  });
   if (int e = core_compact_flags<int>(flags, nchunks, list, count, count + 64, st)) return e;
   MFS_LAUNCH_CHECK();
   int shift = 0;
@@ -1150,106 +918,106 @@ static int vcg_build_classes(mfs_vcg3d* h, hipStream_t stream) {
   h->list_ready = false;
   h->cp.tw_block = 0;
   h->cp.seg_g = 0;
-  if (Nx >= 3 && Ny >= 3) {    // classes of the interior z-vectors for the march's compressed class access
-    const int vec = h->dt == MFS_F32 ? 4 : 2;
-    if (Nz % vec == 0 && Nz >= 2 * vec) {
-      MFS_HIP_TRY(hipMemsetAsync((void*)h->cp.bulk, 0, 8, stream));
-      const int gb = (int)std::min<int64_t>(1024, cdiv(h->cp.stored(), 256));
-      if (h->dt == MFS_F32) hipLaunchKernelGGL((k_vcg_bulk_value<float>), dim3(gb), dim3(256), 0, stream, h->cp, (float*)h->cp.bulk);
-      else hipLaunchKernelGGL((k_vcg_bulk_value<double>), dim3(gb), dim3(256), 0, stream, h->cp, (double*)h->cp.bulk);
-      const int64_t nvec = (int64_t)(Nx - 2) * (Ny - 2) * (Nz / vec);
-      if (h->dt == MFS_F32) hipLaunchKernelGGL((k_vcg_classify<float, 4>), dim3(cdiv(nvec, 256)), dim3(256), 0, stream, h->cp, mp);
-      else hipLaunchKernelGGL((k_vcg_classify<double, 2>), dim3(cdiv(nvec, 256)), dim3(256), 0, stream, h->cp, mp);
-      MFS_LAUNCH_CHECK();
-      // ... and the tile words, for the tile size the march will run with on this grid
-      const int geom = h->dt == MFS_F32 ? vcg_march_geom<float, 4>(h) : vcg_march_geom<double, 2>(h);
-      h->cp.tw_block = geom / 10;
-      if (h->cp.tw_block > 0) {
-        const int ipp = (Ny - 2) * (Nz / vec), tiles = (ipp + h->cp.tw_block - 1) / h->cp.tw_block;
-        const int64_t nt = (int64_t)tiles * Nx;
-        const int64_t gr[3] = {Nx, Ny, Nz};
-        MFS_REQUIRE((size_t)nt <= tile_words_bytes(gr, h->dt), "tile flags do not fit their workspace");
-        unsigned char* const flags = (unsigned char*)h->cp.tw;
-        if (vec == 4) hipLaunchKernelGGL((k_vcg_tile_flags<4>), dim3(cdiv(nt * kWave, 256)), dim3(256), 0, stream, h->cp, h->cp.tw_block, flags);
-        else hipLaunchKernelGGL((k_vcg_tile_flags<2>), dim3(cdiv(nt * kWave, 256)), dim3(256), 0, stream, h->cp, h->cp.tw_block, flags);
-        MFS_LAUNCH_CHECK();
-        // the cost-balanced cut for the grid the march will be launched with on this engine
-        const size_t ldsb = h->dt == MFS_F32 ? (size_t)(geom % 10) * 3 * (2 * Nz + h->cp.tw_block * 4) * 4
-                                             : (size_t)(geom % 10) * 3 * (2 * Nz + h->cp.tw_block * 2) * 8;
-        const int bpc = ldsb > 80 * 1024 ? 1 : h->march_bpc;
-        const int64_t total = (int64_t)tiles * (Nx - 2);
-        const int G = (int)std::max<int64_t>(1, std::min<int64_t>(total, (int64_t)h->c.cus * bpc));
-        h->cp.seg_g = 0;
-        if (G <= kVmMaxSegs && total < 0x7fffffff) {
-          hipLaunchKernelGGL(k_vcg_balance, dim3(1), dim3(1024), 0, stream, flags, tiles, Nx, G, (int*)h->cp.seg);
-          MFS_LAUNCH_CHECK();
-          h->cp.seg_g = G;
-        }
-        // the work list of the CG loop's launches: the busy pairs only (an all-air pair's q is +0 and stays what the
-        // initial q = A x stored there)
-        if (nt < 0x7fffffff && core_compact_scratch_ints(nt) + 16 <= 4096 / sizeof(int)) {      // (the scratch shares the count's page)
-          if (int e = core_compact_flags<unsigned char>(flags, (int)nt, h->list_items, h->list_count, h->list_count + 16, stream)) return e;
-          hipLaunchKernelGGL(k_list_runs, dim3(cdiv(nt, 256)), dim3(256), 0, stream, h->list_items, h->list_count, Nx, h->list_runrem);
-          MFS_LAUNCH_CHECK();
-          h->list_ready = true;
-        }
-      }
-    }
+  const VMarchForm f = vcg_form(h, nullptr, nullptr, false, false);
+  if (!f.rows_ok) return MFS_OK;    // classes of the interior z-vectors for the march's compressed class access
+  const int vec = h->dt == MFS_F32 ? 4 : 2;
+  MFS_HIP_TRY(hipMemsetAsync((void*)h->cp.bulk, 0, 8, stream));
+  const int gb = (int)std::min<int64_t>(1024, cdiv(h->cp.stored(), 256));
+  const int64_t nvec = (int64_t)(Nx - 2) * (Ny - 2) * (Nz / vec);
+  vcg_typed(h, [&](auto t) {
+    typedef decltype(t) T;
+    hipLaunchKernelGGL((k_vcg_bulk_value<T>), dim3(gb), dim3(256), 0, stream, h->cp, (T*)h->cp.bulk);
+    hipLaunchKernelGGL((k_vcg_classify<T, VecOf<T>::N>), dim3(cdiv(nvec, 256)), dim3(256), 0, stream, h->cp, mp);
+  });
+  MFS_LAUNCH_CHECK();
+  // ... and the tile words, for the tile size the march will run with on this grid
+  h->cp.tw_block = f.block;
+  if (f.block == 0) return MFS_OK;
+  const int64_t nt = (int64_t)f.tiles * Nx;
+  const int64_t gr[3] = {Nx, Ny, Nz};
+  MFS_REQUIRE((size_t)nt <= tile_words_bytes(gr, h->dt), "tile flags do not fit their workspace");
+  unsigned char* const flags = (unsigned char*)h->cp.tw;
+  if (vec == 4) hipLaunchKernelGGL((k_vcg_tile_flags<4>), dim3(cdiv(nt * kWave, 256)), dim3(256), 0, stream, h->cp, f.block, flags);
+  else hipLaunchKernelGGL((k_vcg_tile_flags<2>), dim3(cdiv(nt * kWave, 256)), dim3(256), 0, stream, h->cp, f.block, flags);
+  MFS_LAUNCH_CHECK();
+  // the cost-balanced cut for the grid the march will be launched with on this engine
+  if (f.gmain <= kVmMaxSegs && f.total < 0x7fffffff) {
+    hipLaunchKernelGGL(k_vcg_balance, dim3(1), dim3(1024), 0, stream, flags, f.tiles, Nx, f.gmain, (int*)h->cp.seg);
+    MFS_LAUNCH_CHECK();
+    h->cp.seg_g = f.gmain;
+  }
+  // the work list of the CG loop's launches: the busy pairs only (an all-air pair's q is +0 and stays what the
+  // initial q = A x stored there)
+  if (nt < 0x7fffffff && core_compact_scratch_ints(nt) + 16 <= 4096 / sizeof(int)) {      // (the scratch shares the count's page)
+    if (int e = core_compact_flags<unsigned char>(flags, (int)nt, h->list_items, h->list_count, h->list_count + 16, stream)) return e;
+    hipLaunchKernelGGL(k_list_runs, dim3(cdiv(nt, 256)), dim3(256), 0, stream, h->list_items, h->list_count, Nx, h->list_runrem);
+    MFS_LAUNCH_CHECK();
+    h->list_ready = true;
   }
   return MFS_OK;
 }
 
-template <typename T, int VEC, int WAVES>
-static int vcg_march_launch(mfs_vcg3d* h, const Vec3T<T>& vv, T* ob, double* partial, const double* done, hipStream_t st,
-                            int* nparts) {
-  // nontemporal class loads / q stores once operand, result and classes (13 arrays) exceed the Infinity Cache
-  // (MFS_VISC_MARCH_NT = 0 / 1 overrides, read at engine creation)
-  const int knob = h->march_nt;
-  const bool nt = knob < 0 ? (13.0 * (double)h->g.N[0] * h->g.N[1] * h->g.N[2] * sizeof(T) > 200e6) : (knob != 0);
-  if constexpr (VEC == VecOf<T>::N && WAVES == MFS_VMARCH_MIN_WAVES) {
-    // compressed class access (classes, tile flags and the balanced cut built once per set-up, for this tile size)
-    if (h->compress && !h->classes_ready) { if (int e = vcg_build_classes(h, st)) return e; }
-    if (h->compress && h->cp.tw_block > 0 && h->cp.tw_block == vcg_march_geom<T, VEC>(h) / 10)
-      return nt ? vcg_march_launch_nt<T, VEC, WAVES, 5, false, true>(h, vv, ob, partial, done, st, nparts)
-                : vcg_march_launch_nt<T, VEC, WAVES, 0, false, true>(h, vv, ob, partial, done, st, nparts);
-  }
-  return nt ? vcg_march_launch_nt<T, VEC, WAVES, 5>(h, vv, ob, partial, done, st, nparts)
-            : vcg_march_launch_nt<T, VEC, WAVES, 0>(h, vv, ob, partial, done, st, nparts);
+// the run-time march form -> template arguments: f is called with the form's code (vmarch_code) as a
+// std::integral_constant, for the codes of the reachable table only.  false: no kernel was built for the code
+template <class F, size_t... Is>
+static bool vmarch_dispatch(int code, int* err, F&& f, std::index_sequence<Is...>) {
+  constexpr auto codes = vmarch_codes();
+  return ((code == codes[Is] && ((*err = f(std::integral_constant<int, codes[Is]>{})), true)) || ...);
 }
 
-// the stencil launch of fused iteration j >= 1: q = A d_j with d_j = r + beta d_{j-1} formed on the fly and stored to
-// `d_cur`, x += alpha d_{j-1} for every owned face (mfs_vcg_march.h, FUSE)
+// out = A v, ONE launch site for every form (mfs_vcg_form.h); the reachable table of that header has one march kernel per
+// entry and dtype.  d_fused non-null: the stencil launch of fused iteration j >= 1 (mfs_vcg_march.h, FUSE) -- v is d_{j-1},
+// q = A d_j with d_j = r + beta d_{j-1} formed on the fly and stored to d_fused, x += alpha d_{j-1} for every owned face.
 template <typename T>
-static int vcg_march_fused(mfs_vcg3d* h, const void* d_prev, void* d_cur, hipStream_t st, int* nparts) {
+static int vcg_apply_T(mfs_vcg3d* h, const void* v, void* out, double* partial, const double* done, bool masked, hipStream_t st,
+                       int* nparts, void* d_fused) {
   constexpr int VEC = VecOf<T>::N;
-  const T* dp = (const T*)d_prev;
-  T* dc = (T*)d_cur;
-  T* xb = (T*)h->c.x;
-  const T* rb = (const T*)h->c.r;
-  Vec3T<T> vv{{dp + h->off[0], dp + h->off[1], dp + h->off[2]}};
-  VmFuse<T> fz;
-  for (int a = 0; a < 3; ++a) { fz.r[a] = rb + h->off[a]; fz.dn[a] = dc + h->off[a]; fz.x[a] = xb + h->off[a]; }
-  fz.scal = h->c.scal;
-  const int knob = h->march_nt;
-  const bool nt = knob < 0 ? (13.0 * (double)h->g.N[0] * h->g.N[1] * h->g.N[2] * sizeof(T) > 200e6) : (knob != 0);
-  return nt ? vcg_march_launch_nt<T, VEC, MFS_VMARCH_MIN_WAVES, 5, true>(h, vv, (T*)h->c.q, h->c.part_dq, h->c.scal + S_DONE, st, nparts, &fz)
-            : vcg_march_launch_nt<T, VEC, MFS_VMARCH_MIN_WAVES, 0, true>(h, vv, (T*)h->c.q, h->c.part_dq, h->c.scal + S_DONE, st, nparts, &fz);
-}
-
-template <typename T, bool MASK>
-static int vcg_apply_TM(mfs_vcg3d* h, const void* v, void* out, double* partial, const double* done, hipStream_t st,
-                        int* nparts) {
   const T* vb = (const T*)v;
   T* ob = (T*)out;
-  Vec3T<T> vv{{vb + h->off[0], vb + h->off[1], vb + h->off[2]}};
+  const Vec3T<T> vv{{vb + h->off[0], vb + h->off[1], vb + h->off[2]}};
   const int Nx = h->g.N[0], Ny = h->g.N[1], Nz = h->g.N[2];
+  VMarchForm f = vcg_form(h, v, out, masked, d_fused != nullptr);
+  *nparts = 0;
+  if (f.kind == kVApplyNone) return MFS_OK;
+  // compressed class access: classes, tile flags and the balanced cut are built once per set-up, at the first launch that
+  // wants them, for this launch's tile size
+  if (f.kind == kVApplyMarch && f.comp_wanted && !h->classes_ready) {
+    if (int e = vcg_build_classes(h, st)) return e;
+    f = vcg_form(h, v, out, masked, d_fused != nullptr);
+  }
+  MFS_REQUIRE(!d_fused || (f.kind == kVApplyMarch && f.fuse), "fused launch on an engine the fused march cannot serve");
+  const Box3 b0 = vslab_box(h, 0), b1 = vslab_box(h, 1), b2 = vslab_box(h, 2);
+  const int g0 = h->skip_top_x ? 0 : vslab_grid(b0), g1 = vslab_grid(b1), g2 = vslab_grid(b2);
+  if (f.kind == kVApplyMarch) {
+    VmFuse<T> fu{};
+    if (d_fused) {
+      for (int a = 0; a < 3; ++a) { fu.r[a] = (const T*)h->c.r + h->off[a]; fu.dn[a] = (T*)d_fused + h->off[a]; fu.x[a] = (T*)h->c.x + h->off[a]; }
+      fu.scal = h->c.scal;
+    }
+    int err = MFS_OK;
+    const bool launched = vmarch_dispatch(vmarch_code(f.nt, f.fuse, f.block, f.ring, f.comp), &err, [&](auto code) -> int {
+      constexpr VMarchTuple F = vmarch_decode(decltype(code)::value);
+#define MFS_VMARCH_KERNEL k_vcg_apply_march<T, VEC, MFS_VMARCH_MIN_WAVES, F.nt, F.fuse, F.block, F.ring, F.comp>
+      static bool attr_set = false;        // per instantiation: more than the default 64 KB of dynamic LDS
+      if (!attr_set) {
+        MFS_HIP_TRY(hipFuncSetAttribute((const void*)MFS_VMARCH_KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVmMaxLds));
+        attr_set = true;
+      }
+      hipLaunchKernelGGL((MFS_VMARCH_KERNEL), dim3(f.gmain + g0 + g1 + g2), dim3(F.block), f.lds, st, h->cp, h->k1, h->k2, vv, ob + h->off[0],
+                         ob + h->off[1], ob + h->off[2], f.gmain, b0, b1, b2, g0, g1, partial, done, fu);
+#undef MFS_VMARCH_KERNEL
+      return MFS_OK;
+    }, std::make_index_sequence<vmarch_count()>{});
+    MFS_REQUIRE(launched, "march form outside the reachable table of mfs_vcg_form.h");
+    if (err) return err;
+    MFS_LAUNCH_CHECK();
+    *nparts = f.gmain + g0 + g1 + g2;
+    return MFS_OK;
+  }
   int used = 0;
-  if constexpr (sizeof(T) == 4) if (!MASK && !h->tiled && h->march_vec == 2 && vcg_march_ok<T, 2>(h, v, out))
-    return vcg_march_launch<T, 2, 3>(h, vv, ob, partial, done, st, nparts);      // experiment: 8-byte vectors, 3 waves / SIMD
-  if (!MASK && !h->tiled && vcg_march_ok<T>(h, v, out))
-    return vcg_march_launch<T, VecOf<T>::N, MFS_VMARCH_MIN_WAVES>(h, vv, ob, partial, done, st, nparts);
-  // (1) the box where all three rows are interior faces: one fused launch
-  if (Nx >= 3 && Ny >= 3 && Nz >= 3) {
+  if (f.kind == kVApplyAll) {
+    // the box where all three rows are interior faces and the three slabs outside it (u at x = Nx-1, v at y = Ny-1,
+    // w at z = Nz-1), one launch
     const int nbz = (Nz - 2 + 63) / 64, nby = (Ny - 2 + 3) / 4;
     int xchunk = 8;
     while ((int64_t)nbz * nby * ((Nx - 2 + xchunk - 1) / xchunk) > 4096) xchunk *= 2;
@@ -1258,63 +1026,23 @@ static int vcg_apply_TM(mfs_vcg3d* h, const void* v, void* out, double* partial,
     // plain order is faster (256^3: +7 % with it) -- auto unless MFS_VISC_XCD is set
     const double ws = 13.0 * (double)Nx * Ny * Nz * sizeof(T);
     const int xcd = h->xcd_order < 0 ? (ws < 200e6 ? 1 : 0) : h->xcd_order;
-    if (!MASK && h->tiled) {
-      // LDS-staged tiles: 4 x 64 cells (fp32) / 4 x 32 (fp64) so that three planes of ten arrays fit 48 KB
-      constexpr int TZ = sizeof(T) == 4 ? 64 : 32;
-      const int tbz = (Nz - 2 + TZ - 1) / TZ;
-      int xc = h->xchunk_tiled;
-      while ((int64_t)tbz * nby * ((Nx - 2 + xc - 1) / xc) > 4096) xc *= 2;
-      const int tgrid = tbz * nby * ((Nx - 2 + xc - 1) / xc);
-      typedef VTile<T, 4, TZ> Tile;
-      const size_t lds = Tile::lds_bytes();
-      hipLaunchKernelGGL((k_vcg_apply_tiled<T, 4, TZ>), dim3(tgrid), dim3(4 * TZ), lds, st, h->cp,
-                         h->k1, h->k2, vv, ob + h->off[0], ob + h->off[1], ob + h->off[2], xc, tbz, nby, xcd, partial + used,
-                         done);
-      used += tgrid;
-    } else if (h->merge_slabs != 0) {
-      // in-process A/B (tools/visc_ab.py), us per iteration, two launches -> one: 64^3 fp64 35.0 -> 28.0, 128^3 fp32
-      // 70.7 -> 67.4, 192^3 244.8 -> 250.0, 256^3 681 -> 672 (run-to-run and box-to-box spread at 256^3: 618 .. 685)
-      // one launch for the box and the three boundary slabs (below): same partial slots as the two launches
-      const Box3 b0 = vslab_box(h, 0), b1 = vslab_box(h, 1), b2 = vslab_box(h, 2);
-      const int g0 = h->skip_top_x ? 0 : vslab_grid(b0), g1 = vslab_grid(b1), g2 = vslab_grid(b2);
-      hipLaunchKernelGGL((k_vcg_apply_all<T, MASK>), dim3(grid + g0 + g1 + g2), dim3(256), 0, st, h->cp, h->k1, h->k2, vv,
-                         ob + h->off[0], ob + h->off[1], ob + h->off[2], xchunk, nbz, nby, xcd, grid, b0, b1, b2, g0, g1,
-                         partial + used, done);
-      used += grid + g0 + g1 + g2;
-      MFS_LAUNCH_CHECK();
-      *nparts = used;
-      return MFS_OK;
-    } else {
-      hipLaunchKernelGGL((k_vcg_apply_fused<T, MASK>), dim3(grid), dim3(256), 0, st, h->cp, h->k1, h->k2, vv,
-                         ob + h->off[0], ob + h->off[1], ob + h->off[2], xchunk, nbz, nby, xcd, partial + used, done);
-      used += grid;
-    }
-  }
-  // (2) the three slabs of interior faces outside that box: u at x = Nx-1, v at y = Ny-1, w at z = Nz-1
-  auto slab = [&](int ax) { return vslab_box(h, ax); };
-  auto sgrid = [&](const Box3& b) { return vslab_grid(b); };
-  if (Nx >= 3 && Ny >= 3 && Nz >= 3) {
-    const Box3 b0 = slab(0), b1 = slab(1), b2 = slab(2);
-    const int g0 = h->skip_top_x ? 0 : sgrid(b0), g1 = sgrid(b1), g2 = sgrid(b2);
-    hipLaunchKernelGGL((k_vcg_apply_slabs<T, MASK>), dim3(g0 + g1 + g2), dim3(256), 0, st, h->cp, h->k1, h->k2, vv,
-                       ob + h->off[0], ob + h->off[1], ob + h->off[2], b0, b1, b2, g0, g1, partial + used, done);
-    used += g0 + g1 + g2;
+#define MFS_VALL(MASK) \
+    hipLaunchKernelGGL((k_vcg_apply_all<T, MASK>), dim3(grid + g0 + g1 + g2), dim3(256), 0, st, h->cp, h->k1, h->k2, vv, ob + h->off[0], \
+                       ob + h->off[1], ob + h->off[2], xchunk, nbz, nby, xcd, grid, b0, b1, b2, g0, g1, partial, done)
+    if (masked) MFS_VALL(true); else MFS_VALL(false);
+#undef MFS_VALL
+    used = grid + g0 + g1 + g2;
   } else {   // degenerate grids: whichever slabs exist, one launch each
-    if (Nx >= 2 && Ny >= 3 && Nz >= 3 && !h->skip_top_x) {
-      const Box3 b = slab(0); const int g = sgrid(b);
-      hipLaunchKernelGGL((k_vcg_apply_row<T, 0, MASK>), dim3(g), dim3(256), 0, st, h->cp, h->k1, h->k2, vv, ob + h->off[0], b, partial + used, done);
-      used += g;
-    }
-    if (Nx >= 3 && Ny >= 2 && Nz >= 3) {
-      const Box3 b = slab(1); const int g = sgrid(b);
-      hipLaunchKernelGGL((k_vcg_apply_row<T, 1, MASK>), dim3(g), dim3(256), 0, st, h->cp, h->k1, h->k2, vv, ob + h->off[1], b, partial + used, done);
-      used += g;
-    }
-    if (Nx >= 3 && Ny >= 3 && Nz >= 2) {
-      const Box3 b = slab(2); const int g = sgrid(b);
-      hipLaunchKernelGGL((k_vcg_apply_row<T, 2, MASK>), dim3(g), dim3(256), 0, st, h->cp, h->k1, h->k2, vv, ob + h->off[2], b, partial + used, done);
-      used += g;
-    }
+#define MFS_VROW(AX, BOX, G) \
+    do { \
+      if (masked) hipLaunchKernelGGL((k_vcg_apply_row<T, AX, true>), dim3(G), dim3(256), 0, st, h->cp, h->k1, h->k2, vv, ob + h->off[AX], BOX, partial + used, done); \
+      else hipLaunchKernelGGL((k_vcg_apply_row<T, AX, false>), dim3(G), dim3(256), 0, st, h->cp, h->k1, h->k2, vv, ob + h->off[AX], BOX, partial + used, done); \
+      used += G; \
+    } while (0)
+    if (Nx >= 2 && Ny >= 3 && Nz >= 3 && !h->skip_top_x) MFS_VROW(0, b0, g0);
+    if (Nx >= 3 && Ny >= 2 && Nz >= 3) MFS_VROW(1, b1, g1);
+    if (Nx >= 3 && Ny >= 3 && Nz >= 2) MFS_VROW(2, b2, g2);
+#undef MFS_VROW
   }
   MFS_LAUNCH_CHECK();
   *nparts = used;
@@ -1322,15 +1050,10 @@ static int vcg_apply_TM(mfs_vcg3d* h, const void* v, void* out, double* partial,
 }
 
 // masked = false only for operands that are 0 on solid / array-boundary faces (the CG's d)
-static int vcg_apply(mfs_vcg3d* h, const void* v, void* out, double* partial, bool use_done, bool masked,
-                     hipStream_t st, int* nparts) {
-  if (h->g.N[0] < 2 || h->g.N[1] < 2 || h->g.N[2] < 2) { *nparts = 0; return MFS_OK; }
+static int vcg_apply(mfs_vcg3d* h, const void* v, void* out, double* partial, bool use_done, bool masked, hipStream_t st,
+                     int* nparts, void* d_fused = nullptr) {
   const double* done = use_done ? h->c.scal + S_DONE : nullptr;
-  if (h->dt == MFS_F32)
-    return masked ? vcg_apply_TM<float, true>(h, v, out, partial, done, st, nparts)
-                  : vcg_apply_TM<float, false>(h, v, out, partial, done, st, nparts);
-  return masked ? vcg_apply_TM<double, true>(h, v, out, partial, done, st, nparts)
-                : vcg_apply_TM<double, false>(h, v, out, partial, done, st, nparts);
+  return vcg_typed(h, [&](auto t) { return vcg_apply_T<decltype(t)>(h, v, out, partial, done, masked, st, nparts, d_fused); });
 }
 
 // ---- window transport of the slab loop (mfs_p2p.h): the edge planes of the direction vector and the two dot products
@@ -1421,7 +1144,7 @@ struct VcgListScope {
   mfs_vcg3d* h;
   int err = MFS_OK;
   VcgListScope(mfs_vcg3d* h_, hipStream_t st) : h(h_) {
-    if (h->c.live.list && h->compress && !h->mask_cg) {
+    if (h->c.live.list && h->compress) {
       if (!h->classes_ready) err = vcg_build_classes(h, st);
       if (!err && h->list_ready) { h->cp.items = h->list_items; h->cp.runrem = h->list_runrem; h->cp.count = h->list_count; }
     }
@@ -1447,7 +1170,7 @@ static int vslab_iteration(mfs_vcg3d* h, hipStream_t st) {
   {
     VcgListScope list(h, st);
     if (list.err) return list.err;
-    if ((e = vcg_apply(h, h->c.d, h->c.q, h->c.part_dq, true, h->mask_cg != 0, st, &np))) return e;
+    if ((e = vcg_apply(h, h->c.d, h->c.q, h->c.part_dq, true, false, st, &np))) return e;
   }
   h->c.n_part_dq = np;
   if (h->jacobi) {
@@ -1651,6 +1374,153 @@ static int vcg_build_diag(mfs_vcg3d* h, hipStream_t st) {
   return MFS_OK;
 }
 
+// Which loop mfs_vcg3d_iterate runs and whether begin builds the solve's sparse lists: decided by vloop_form
+// (mfs_vcg_form.h) and nowhere else, from the engine as it stands at the call (bound pointers, knobs: never cached), for
+// iterate, loop_info, poll, solve, begin and slab_begin alike.
+static VLoopForm vcg_loop_form(const mfs_vcg3d* h) {
+  VLoopInputs in{};
+  in.bound = h->c.x != nullptr; in.is_setup = h->is_setup; in.d_bound = h->c.d != nullptr;
+  in.vec_ok = core_vec_ok(h->c); in.rdx_ok = core_rdx_ok(h->c);
+  in.jacobi = h->jacobi != 0; in.fuse = h->fuse != 0; in.split_x = h->split_x != 0; in.jacobi_z = h->jacobi_z;
+  in.resident = h->resident != 0; in.res_fits = h->res.ok && h->res_ar && h->c.cus >= h->res.W;
+  in.p2p = h->p2p != nullptr; in.skip_top_x = h->skip_top_x != 0;
+  if (in.fuse) {      // can the fused march serve d -> q as bound?
+    const VMarchForm mf = vcg_form(h, h->c.d, h->c.q, false, true);
+    in.fuse_march = mf.kind == kVApplyMarch && mf.fuse;
+  }
+  in.n = h->n; in.elt = dtype_size(h->dt);
+  return vloop_form(in);
+}
+
+// r = b - q, d = z = r / diag with the partials of r.r and r.z: the initial residual of the opt-in Jacobi loop
+// (mfs_vcg3d_begin, mfs_vcg3d_slab_begin)
+static int vcg_jac_init(mfs_vcg3d* h, hipStream_t st) {
+  if (int e = vcg_build_diag(h, st)) return e;
+  const int g2 = std::max(1, (int)std::min<int64_t>(h->c.grid_vec, (h->n + kBlock - 1) / kBlock));
+  vcg_typed(h, [&](auto t) {
+    typedef decltype(t) T;
+    hipLaunchKernelGGL((k_jac_init<T>), dim3(g2), dim3(kBlock), 0, st, (const T*)h->c.b, (const T*)h->c.q, (const T*)h->diag,
+                       (T*)h->c.d, (T*)h->c.r, h->n, h->c.part_rr, h->part_rz);
+  });
+  MFS_LAUNCH_CHECK();
+  h->c.n_part_rr = g2;
+  return MFS_OK;
+}
+
+// one iteration of the opt-in Jacobi loop: stencil launch, x / r update with r.r and r.z (z = r / diag formed on the fly),
+// direction update d = z + beta d with the bookkeeping -- the generic kernels of mfs_cg_core.h on the flat vectors
+template <typename T, int VEC>
+static int vcg_jac_iteration(mfs_vcg3d* h, hipStream_t st) {
+  int e, np = 0;
+  if ((e = vcg_apply(h, h->c.d, h->c.q, h->c.part_dq, true, false, st, &np))) return e;
+  h->c.n_part_dq = np;
+  const int grid = core_vec_grid(h->c, VEC > 1);
+  const int par = (int)(h->c.iter_enq & 1);
+  hipLaunchKernelGGL((k_jac_update_xr<T, VEC>), dim3(grid), dim3(kBlock), 0, st, (T*)h->c.x, (const T*)h->c.d, (T*)h->c.r,
+                     (const T*)h->c.q, (const T*)h->diag, h->n, h->c.scal, h->c.part_rr, h->part_rz, par, h->c.part_dq,
+                     h->c.n_part_dq);
+  hipLaunchKernelGGL((k_jac_update_d<T, VEC>), dim3(grid), dim3(kBlock), 0, st, (T*)h->c.d, (const T*)h->c.r,
+                     (const T*)h->diag, h->n, h->c.scal, h->c.hist, kHistCap, par, h->c.part_rr, h->part_rz, grid);
+  MFS_LAUNCH_CHECK();
+  h->c.n_part_rr = grid;
+  ++h->c.iter_enq;
+  return MFS_OK;
+}
+
+// the same iteration with z STORED (aligned vectors): the r update reads diag once, writes r and z = r / diag (into the
+// fused loop's partner buffer, idle here) and its last block closes the iteration; the second phase x += alpha d,
+// d = z + beta d streams five arrays.  10 instead of 11 scalars per DOF, two reduction-free streaming kernels:
+// 256^3 fp32 660 -> see profiles/r02_jacobi_time_step.txt
+template <typename T, int VEC>
+static int vcg_jac_iteration_z(mfs_vcg3d* h, hipStream_t st) {
+  int e, np = 0;
+  if ((e = vcg_apply(h, h->c.d, h->c.q, h->c.part_dq, true, false, st, &np))) return e;
+  h->c.n_part_dq = np;
+  const int grid = core_vec_grid(h->c, true);
+  const int par = (int)(h->c.iter_enq & 1);
+  hipLaunchKernelGGL((k_jac_update_rz<T, VEC, false>), dim3(grid), dim3(kBlock), 0, st, (T*)h->c.x, (const T*)h->c.d, (T*)h->c.r,
+                     (const T*)h->c.q, (const T*)h->diag, (T*)h->d2, h->n, h->c.scal, h->c.part_rr, h->part_rz, par,
+                     h->c.part_dq, h->c.n_part_dq, (const unsigned char*)nullptr, h->c.hist, kHistCap, h->c.tickets, JacSlab{}, h->c.live);
+  const bool ntx = 5.0 * (double)h->n * h->c.elt > 200e6;
+  if (ntx) hipLaunchKernelGGL((k_jac_dx<T, VEC, true>), dim3(grid), dim3(kBlock), 0, st, (T*)h->c.x, (T*)h->c.d, (const T*)h->d2, h->n,
+                              h->c.scal, (double)h->c.iter_enq, h->c.live);
+  else hipLaunchKernelGGL((k_jac_dx<T, VEC, false>), dim3(grid), dim3(kBlock), 0, st, (T*)h->c.x, (T*)h->c.d, (const T*)h->d2, h->n,
+                          h->c.scal, (double)h->c.iter_enq, h->c.live);
+  MFS_LAUNCH_CHECK();
+  h->c.n_part_rr = grid;
+  ++h->c.iter_enq;
+  return MFS_OK;
+}
+
+// the resident loop (mfs_vcg_resident.h): one launch per batch
+template <typename T>
+static int vcg_launch_resident(mfs_vcg3d* h, const VResArgs& a, hipStream_t st) {
+  const VResPlan& p = h->res;
+#define MFS_VRES_ONE(KCC, CRG)                                                                                   \
+  do {                                                                                                           \
+    MFS_HIP_TRY(hipFuncSetAttribute((const void*)k_vcg_resident<T, KCC, CRG>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                    (int)kVResLdsMax));                                                          \
+    hipLaunchKernelGGL((k_vcg_resident<T, KCC, CRG>), dim3(p.W), dim3(kVResBlock), p.lds, st, a);                \
+  } while (0)
+  // volume samples in registers where KC cells' worth fit without spills (16 per cell, kept converted to fp64):
+  // 8-byte state up to 2 cells, 4-byte up to 3
+  const bool creg = h->res_creg != 0 && p.kc <= (sizeof(T) == 8 ? 2 : 3);
+  if (p.kc <= 1) { if (creg) MFS_VRES_ONE(1, true); else MFS_VRES_ONE(1, false); }
+  else if (p.kc == 2) { if (creg) MFS_VRES_ONE(2, true); else MFS_VRES_ONE(2, false); }
+  else if (p.kc == 3) { if (creg) MFS_VRES_ONE(3, true); else MFS_VRES_ONE(3, false); }
+  else if (p.kc == 4) MFS_VRES_ONE(4, false);
+  else MFS_VRES_ONE(6, false);
+#undef MFS_VRES_ONE
+  MFS_LAUNCH_CHECK();
+  return MFS_OK;
+}
+
+static int vcg_iterate_resident(mfs_vcg3d* h, int64_t n, hipStream_t st) {
+  while (n > 0) {
+    const int nb = (int)std::min<int64_t>(n, 1 << 20);
+    if (h->res_epoch > 0xf0000000u - 2u * (unsigned)nb) {      // tags about to wrap: start over on clean tables
+      MFS_HIP_TRY(hipMemsetAsync(h->res_ar, 0, vres_ws_bytes(h->n, h->c.elt), st));
+      h->res_epoch = 0;
+    }
+    VResArgs a{};
+    a.x = h->c.x; a.r = h->c.r; a.q = h->c.q; a.d = h->c.d;
+    a.c = h->cp; a.k1 = h->k1; a.k2 = h->k2;
+    for (int c = 0; c < 3; ++c) a.off[c] = h->off[c];
+    a.Px = h->res.Px; a.Py = h->res.Py; a.bxm = h->res.bxm; a.bym = h->res.bym;
+    a.scal = h->c.scal; a.hist = h->c.hist; a.hist_cap = kHistCap;
+    a.n_iter = nb;
+    a.ar = h->res_ar; a.mirror = h->res_mirror;
+    a.tag0 = h->res_epoch + 1u;
+    a.timeout_ticks = h->res_timeout_ticks; a.first_timeout_ticks = h->res_first_timeout_ticks;
+    a.test_drop_wg = h->res_drop_wg;
+    int e = h->dt == MFS_F32 ? vcg_launch_resident<float>(h, a, st) : vcg_launch_resident<double>(h, a, st);
+    if (e) return e;
+    h->res_epoch += 2u * (unsigned)nb;
+    h->c.iter_enq += nb;
+    n -= nb;
+  }
+  return MFS_OK;
+}
+
+// what the fused loop owes when it stops after `iters` completed iterations: x += alpha d of the last one, the direction
+// update d_iters = r + beta d_{iters-1} unless it converged (the reference updates d at the end of every non-converged
+// iteration, :609-610), and d brought home to the bound array if it sits in the partner buffer
+static int vcg_home(mfs_vcg3d* h, int64_t iters, bool converged, hipStream_t st) {
+  if (!h->fused_run) return MFS_OK;
+  h->fused_run = false;
+  if (iters < 1) return MFS_OK;
+  void* cur = ((iters - 1) & 1) ? h->d2 : h->c.d;             // holds d_{iters-1}
+  const int grid = core_vec_grid(h->c, true);
+  vcg_typed(h, [&](auto t) {
+    typedef decltype(t) T;
+    hipLaunchKernelGGL((k_x_axpy<T, VecOf<T>::N>), dim3(grid), dim3(kBlock), 0, st, (T*)h->c.x, (const T*)cur, h->n, h->c.scal);
+    if (!converged) hipLaunchKernelGGL((k_d_axpy<T, VecOf<T>::N>), dim3(grid), dim3(kBlock), 0, st, (T*)cur, (const T*)h->c.r, h->n, h->c.scal);
+  });
+  MFS_LAUNCH_CHECK();
+  if (cur != h->c.d) MFS_HIP_TRY(hipMemcpyAsync(h->c.d, cur, (size_t)h->n * h->c.elt, hipMemcpyDeviceToDevice, st));
+  return MFS_OK;
+}
+
 extern "C" {
 
 // ------------------------------------------------------------------ engine ---
@@ -1732,6 +1602,7 @@ int mfs_vcg3d_create(mfs_vcg3d** out, const int64_t gres[3], int dt, void* works
   h->res_drop_wg = env_int("MFS_VRES_TEST_DROP_WG", -1);
   h->res_creg = env_int("MFS_VRES_CREG", 1);
   h->jacobi = env_int("MFS_VISC_JACOBI", 0);
+  h->jacobi_z = env_int("MFS_VISC_JACOBI_Z", -1);
   h->last_iters = 0;
   h->diag_ready = false;
   h->compress = env_int("MFS_VISC_COMPRESS", 1);
@@ -1744,17 +1615,13 @@ int mfs_vcg3d_create(mfs_vcg3d** out, const int64_t gres[3], int dt, void* works
   h->fused_run = false;
   h->grid_row = std::min(kMaxPartials / 3, h->c.cus * env_int("MFS_VISC_BLOCKS_PER_CU", 8));
   h->is_setup = false;
-  h->mask_cg = env_int("MFS_VISC_MASK_CG", 0);
-  h->tiled = env_int("MFS_VISC_TILED", 0);   // measured slower than the direct-load kernel; kept selectable
   h->xcd_order = env_int("MFS_VISC_XCD", -1);
   h->split_x = env_int("MFS_VISC_SPLIT_X", 1);
   h->skip_top_x = 0;
   h->p2p = nullptr;
-  h->merge_slabs = env_int("MFS_VISC_MERGE", 1);
   h->march = env_int("MFS_VISC_MARCH", 1);
   h->march_bpc = std::max(1, env_int("MFS_VISC_MARCH_BPC", 2));
-  h->march_vec = env_int("MFS_VISC_MARCH_VEC", 0);
-  h->xchunk_tiled = std::max(1, env_int("MFS_VISC_XCHUNK", 32));
+  h->march_block = env_int("MFS_VISC_MARCH_BLOCK", 0);
   h->k1 = h->k2 = 0.0;
   if (hipMemsetAsync(workspace, 0, mfs_vcg3d_workspace_bytes(gres, dt), (hipStream_t)stream) != hipSuccess) {
     set_error("hipMemsetAsync(workspace) failed");
@@ -1782,14 +1649,11 @@ int mfs_vcg3d_setup(mfs_vcg3d* h, double scale, double mu, const void* sphi, int
   unsigned char* mp = (unsigned char*)h->cp.msk;
   MFS_HIP_TRY(hipMemsetAsync(mp, 0, align_up((size_t)h->cp.stored(), 4), (hipStream_t)stream));   // the setup kernel ORs bits in
   void* const* v = (void* const*)h->cp.vol;
-  if (h->dt == MFS_F32)
-    hipLaunchKernelGGL((k_vcg_setup<float>), dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, Nx, Ny, Nz, h->cp.py,
-                       h->cp.pz, sphi, sphi_dt, vol, vol_dt, (float*)v[1], (float*)v[2], (float*)v[3], (float*)v[4], (float*)v[5],
-                       (float*)v[6], (float*)v[7], mp);
-  else
-    hipLaunchKernelGGL((k_vcg_setup<double>), dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, Nx, Ny, Nz, h->cp.py,
-                       h->cp.pz, sphi, sphi_dt, vol, vol_dt, (double*)v[1], (double*)v[2], (double*)v[3], (double*)v[4],
-                       (double*)v[5], (double*)v[6], (double*)v[7], mp);
+  vcg_typed(h, [&](auto t) {
+    typedef decltype(t) T;
+    hipLaunchKernelGGL((k_vcg_setup<T>), dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, Nx, Ny, Nz, h->cp.py, h->cp.pz, sphi,
+                       sphi_dt, vol, vol_dt, (T*)v[1], (T*)v[2], (T*)v[3], (T*)v[4], (T*)v[5], (T*)v[6], (T*)v[7], mp);
+  });
   MFS_LAUNCH_CHECK();
   h->classes_ready = false;    // the march's compressed class access builds its classes at its first launch (vcg_build_classes)
   h->list_ready = false;
@@ -1812,12 +1676,7 @@ int mfs_vcg3d_apply(mfs_vcg3d* h, const void* v, void* out, mfs_stream stream) {
 
 int mfs_vcg3d_apply_kernel(mfs_vcg3d* h) {
   if (!h) return 0;
-  if (h->tiled) return 1;
-  static const char aligned[16] __attribute__((aligned(16))) = {0};
-  const void* d = h->c.d ? h->c.d : (const void*)aligned;
-  const void* q = h->c.q ? h->c.q : (const void*)aligned;
-  const bool ok = h->dt == MFS_F32 ? vcg_march_ok<float>(h, d, q) : vcg_march_ok<double>(h, d, q);
-  return ok ? 2 : 0;
+  return vcg_form(h, h->c.d, h->c.q, false, false).kind == kVApplyMarch ? 2 : 0;      // (unbound vectors count as aligned)
 }
 
 int mfs_vcg3d_bind(mfs_vcg3d* h, void* b, void* x, void* d, void* r, void* q) {
@@ -1833,30 +1692,23 @@ int mfs_vcg3d_begin(mfs_vcg3d* h, double tol, mfs_stream stream) {
   if (int e = core_begin_pre(h->c, tol, false, st)) return e;     // x keeps the extrapolated velocity (:569-573)
   int np = 0;
   if (int e = vcg_apply(h, h->c.x, h->c.q, h->c.part_dq, false, true, st, &np)) return e;   // :575
+  const bool lists = vcg_loop_form(h).lists_begin;      // single-domain, launch-per-phase loops only
   if (h->jacobi) {       // opt-in: r = b - q, d = z = r / diag, delta0 = r.z (stopping rule stays r.r < tol^2)
-    if (int e = vcg_build_diag(h, st)) return e;
-    const int g2 = std::max(1, (int)std::min<int64_t>(h->c.grid_vec, (h->n + kBlock - 1) / kBlock));
-    if (h->dt == MFS_F32)
-      hipLaunchKernelGGL((k_jac_init<float>), dim3(g2), dim3(kBlock), 0, st, (const float*)h->c.b, (const float*)h->c.q,
-                         (const float*)h->diag, (float*)h->c.d, (float*)h->c.r, h->n, h->c.part_rr, h->part_rz);
-    else
-      hipLaunchKernelGGL((k_jac_init<double>), dim3(g2), dim3(kBlock), 0, st, (const double*)h->c.b, (const double*)h->c.q,
-                         (const double*)h->diag, (double*)h->c.d, (double*)h->c.r, h->n, h->c.part_rr, h->part_rz);
-    h->c.n_part_rr = g2;
-    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(kBlock), 0, st, h->c.part_rr, g2, h->c.scal, (int)S_RR, 0);
-    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(kBlock), 0, st, h->part_rz, g2, h->c.scal, (int)S_RZ, 0);
+    if (int e = vcg_jac_init(h, st)) return e;
+    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(kBlock), 0, st, h->c.part_rr, h->c.n_part_rr, h->c.scal, (int)S_RR, 0);
+    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(kBlock), 0, st, h->part_rz, h->c.n_part_rr, h->c.scal, (int)S_RZ, 0);
     hipLaunchKernelGGL(k_jac_begin_finish, dim3(1), dim3(64), 0, st, h->c.scal, h->c.hist);
     MFS_LAUNCH_CHECK();
     // the solve's sparse lists for the opt-in Jacobi loop too (z = r / diag is 0 wherever r is: a dead face stays dead); the
     // stored z (the z form keeps it in the fused loop's partner buffer) must then be 0 outside the live chunks
-    if (h->p2p || h->skip_top_x) return MFS_OK;
+    if (!lists) return MFS_OK;
     if (int e = vcg_build_live(h, st)) return e;
     if (h->c.live.list) MFS_HIP_TRY(hipMemsetAsync(h->d2, 0, (size_t)h->n * h->c.elt, st));
     return MFS_OK;
   }
   if (int e = core_begin_post(h->c, st)) return e;                // :577-585
   if (int e = core_begin_finish(h->c, st)) return e;
-  return (h->p2p || h->skip_top_x || h->fuse) ? MFS_OK : vcg_build_live(h, st);      // single-domain, launch-per-phase loops only
+  return lists ? vcg_build_live(h, st) : MFS_OK;
 }
 
 // ---- slab decomposition along x (mfs/dist.py:SlabVCG): the phases of one iteration, so that the caller can put the
@@ -1890,7 +1742,7 @@ int mfs_vcg3d_begin_finish(mfs_vcg3d* h, mfs_stream stream) {
 int mfs_vcg3d_phase_apply(mfs_vcg3d* h, mfs_stream stream) {
   MFS_REQUIRE(h && h->c.d && h->is_setup, "engine not bound / set up");
   int np = 0;
-  if (int e = vcg_apply(h, h->c.d, h->c.q, h->c.part_dq, true, h->mask_cg != 0, (hipStream_t)stream, &np)) return e;
+  if (int e = vcg_apply(h, h->c.d, h->c.q, h->c.part_dq, true, false, (hipStream_t)stream, &np)) return e;
   h->c.n_part_dq = np;
   return MFS_OK;
 }
@@ -1935,16 +1787,7 @@ int mfs_vcg3d_slab_begin(mfs_vcg3d* h, double tol, mfs_stream stream) {
   int np = 0;
   if (int e = vcg_apply(h, h->c.x, h->c.q, h->c.part_dq, false, true, st, &np)) return e;
   if (h->jacobi) {       // r = b - q, d = z = r / diag; r.r and r.z over all ranks (episodes 0 and 1); delta0 = r.z
-    if (int e = vcg_build_diag(h, st)) return e;
-    const int g2 = std::max(1, (int)std::min<int64_t>(h->c.grid_vec, (h->n + kBlock - 1) / kBlock));
-    if (h->dt == MFS_F32)
-      hipLaunchKernelGGL((k_jac_init<float>), dim3(g2), dim3(kBlock), 0, st, (const float*)h->c.b, (const float*)h->c.q,
-                         (const float*)h->diag, (float*)h->c.d, (float*)h->c.r, h->n, h->c.part_rr, h->part_rz);
-    else
-      hipLaunchKernelGGL((k_jac_init<double>), dim3(g2), dim3(kBlock), 0, st, (const double*)h->c.b, (const double*)h->c.q,
-                         (const double*)h->diag, (double*)h->c.d, (double*)h->c.r, h->n, h->c.part_rr, h->part_rz);
-    MFS_LAUNCH_CHECK();
-    h->c.n_part_rr = g2;
+    if (int e = vcg_jac_init(h, st)) return e;
     if (int e = vslab_allreduce(h, S_RR, 0, 0, st)) return e;
     if (int e = vslab_allreduce(h, S_RZ, 0, 1, st)) return e;
     hipLaunchKernelGGL(k_jac_begin_finish, dim3(1), dim3(64), 0, st, h->c.scal, h->c.hist);
@@ -1956,7 +1799,7 @@ int mfs_vcg3d_slab_begin(mfs_vcg3d* h, double tol, mfs_stream stream) {
   if (int e = core_begin_finish(h->c, st)) return e;
   // (a face's liveness is a property of its own rank: an empty row gives q = 0 whatever the ghost planes hold; ghost faces are
   // array-boundary faces of the local arrays -- never swept unless they share a chunk with a live face, as in the dense loop)
-  return h->fuse ? MFS_OK : vcg_build_live(h, st);
+  return vcg_loop_form(h).lists_slab ? vcg_build_live(h, st) : MFS_OK;
 }
 
 int mfs_vcg3d_slab_iterate(mfs_vcg3d* h, int64_t n, mfs_stream stream) {
@@ -1968,140 +1811,25 @@ int mfs_vcg3d_slab_iterate(mfs_vcg3d* h, int64_t n, mfs_stream stream) {
   return MFS_OK;
 }
 
-// can the fused loop serve the engine as bound?  (the marching kernel's preconditions, 16-byte aligned CG vectors)
-static bool vcg_fuse_ok(const mfs_vcg3d* h) {
-  if ((h->dt == MFS_F32 ? vcg_march_geom<float, 4>(h) : vcg_march_geom<double, 2>(h)) % 10 == 3) return false;   // (no fused form on the 3-slot ring)
-  if (!h->fuse || h->jacobi || !h->split_x || h->mask_cg || h->tiled || h->march_vec == 2 || !h->c.d || !core_vec_ok(h->c)) return false;
-  return h->dt == MFS_F32 ? vcg_march_ok<float>(h, h->c.d, h->c.q) : vcg_march_ok<double>(h, h->c.d, h->c.q);
-}
-
-extern "C++" {
-// one iteration of the opt-in Jacobi loop: stencil launch, x / r update with r.r and r.z (z = r / diag formed on the fly),
-// direction update d = z + beta d with the bookkeeping -- the generic kernels of mfs_cg_core.h on the flat vectors
-template <typename T, int VEC>
-static int vcg_jac_iteration(mfs_vcg3d* h, hipStream_t st) {
-  int e, np = 0;
-  if ((e = vcg_apply(h, h->c.d, h->c.q, h->c.part_dq, true, false, st, &np))) return e;
-  h->c.n_part_dq = np;
-  const int grid = core_vec_grid(h->c, VEC > 1);
-  const int par = (int)(h->c.iter_enq & 1);
-  hipLaunchKernelGGL((k_jac_update_xr<T, VEC>), dim3(grid), dim3(kBlock), 0, st, (T*)h->c.x, (const T*)h->c.d, (T*)h->c.r,
-                     (const T*)h->c.q, (const T*)h->diag, h->n, h->c.scal, h->c.part_rr, h->part_rz, par, h->c.part_dq,
-                     h->c.n_part_dq);
-  hipLaunchKernelGGL((k_jac_update_d<T, VEC>), dim3(grid), dim3(kBlock), 0, st, (T*)h->c.d, (const T*)h->c.r,
-                     (const T*)h->diag, h->n, h->c.scal, h->c.hist, kHistCap, par, h->c.part_rr, h->part_rz, grid);
-  MFS_LAUNCH_CHECK();
-  h->c.n_part_rr = grid;
-  ++h->c.iter_enq;
-  return MFS_OK;
-}
-
-// the same iteration with z STORED (aligned vectors): the r update reads diag once, writes r and z = r / diag (into the
-// fused loop's partner buffer, idle here) and its last block closes the iteration; the second phase x += alpha d,
-// d = z + beta d streams five arrays.  10 instead of 11 scalars per DOF, two reduction-free streaming kernels:
-// 256^3 fp32 660 -> see profiles/r02_jacobi_time_step.txt
-template <typename T, int VEC>
-static int vcg_jac_iteration_z(mfs_vcg3d* h, hipStream_t st) {
-  int e, np = 0;
-  if ((e = vcg_apply(h, h->c.d, h->c.q, h->c.part_dq, true, false, st, &np))) return e;
-  h->c.n_part_dq = np;
-  const int grid = core_vec_grid(h->c, true);
-  const int par = (int)(h->c.iter_enq & 1);
-  hipLaunchKernelGGL((k_jac_update_rz<T, VEC, false>), dim3(grid), dim3(kBlock), 0, st, (T*)h->c.x, (const T*)h->c.d, (T*)h->c.r,
-                     (const T*)h->c.q, (const T*)h->diag, (T*)h->d2, h->n, h->c.scal, h->c.part_rr, h->part_rz, par,
-                     h->c.part_dq, h->c.n_part_dq, (const unsigned char*)nullptr, h->c.hist, kHistCap, h->c.tickets, JacSlab{}, h->c.live);
-  const bool ntx = 5.0 * (double)h->n * h->c.elt > 200e6;
-  if (ntx) hipLaunchKernelGGL((k_jac_dx<T, VEC, true>), dim3(grid), dim3(kBlock), 0, st, (T*)h->c.x, (T*)h->c.d, (const T*)h->d2, h->n,
-                              h->c.scal, (double)h->c.iter_enq, h->c.live);
-  else hipLaunchKernelGGL((k_jac_dx<T, VEC, false>), dim3(grid), dim3(kBlock), 0, st, (T*)h->c.x, (T*)h->c.d, (const T*)h->d2, h->n,
-                          h->c.scal, (double)h->c.iter_enq, h->c.live);
-  MFS_LAUNCH_CHECK();
-  h->c.n_part_rr = grid;
-  ++h->c.iter_enq;
-  return MFS_OK;
-}
-}  // extern "C++"
-
-// the resident loop (mfs_vcg_resident.h): a grid whose state fits W workgroups' registers and LDS, the reference's plain
-// loop (no Jacobi, no fused / masked / slab form), a device with that many CUs
-static bool vcg_resident_ok(const mfs_vcg3d* h) {
-  return h->resident != 0 && h->res.ok && h->res_ar && !h->jacobi && !h->fuse && !h->mask_cg && !h->p2p && !h->skip_top_x &&
-         h->c.x && h->c.cus >= h->res.W;
-}
-
-extern "C++" {
-template <typename T>
-static int vcg_launch_resident(mfs_vcg3d* h, const VResArgs& a, hipStream_t st) {
-  const VResPlan& p = h->res;
-#define MFS_VRES_ONE(KCC, CRG)                                                                                   \
-  do {                                                                                                           \
-    MFS_HIP_TRY(hipFuncSetAttribute((const void*)k_vcg_resident<T, KCC, CRG>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    (int)kVResLdsMax));                                                          \
-    hipLaunchKernelGGL((k_vcg_resident<T, KCC, CRG>), dim3(p.W), dim3(kVResBlock), p.lds, st, a);                \
-  } while (0)
-  // volume samples in registers where KC cells' worth fit without spills (16 per cell, kept converted to fp64):
-  // 8-byte state up to 2 cells, 4-byte up to 3
-  const bool creg = h->res_creg != 0 && p.kc <= (sizeof(T) == 8 ? 2 : 3);
-  if (p.kc <= 1) { if (creg) MFS_VRES_ONE(1, true); else MFS_VRES_ONE(1, false); }
-  else if (p.kc == 2) { if (creg) MFS_VRES_ONE(2, true); else MFS_VRES_ONE(2, false); }
-  else if (p.kc == 3) { if (creg) MFS_VRES_ONE(3, true); else MFS_VRES_ONE(3, false); }
-  else if (p.kc == 4) MFS_VRES_ONE(4, false);
-  else MFS_VRES_ONE(6, false);
-#undef MFS_VRES_ONE
-  MFS_LAUNCH_CHECK();
-  return MFS_OK;
-}
-}  // extern "C++"
-
-static int vcg_iterate_resident(mfs_vcg3d* h, int64_t n, hipStream_t st) {
-  while (n > 0) {
-    const int nb = (int)std::min<int64_t>(n, 1 << 20);
-    if (h->res_epoch > 0xf0000000u - 2u * (unsigned)nb) {      // tags about to wrap: start over on clean tables
-      MFS_HIP_TRY(hipMemsetAsync(h->res_ar, 0, vres_ws_bytes(h->n, h->c.elt), st));
-      h->res_epoch = 0;
-    }
-    VResArgs a{};
-    a.x = h->c.x; a.r = h->c.r; a.q = h->c.q; a.d = h->c.d;
-    a.c = h->cp; a.k1 = h->k1; a.k2 = h->k2;
-    for (int c = 0; c < 3; ++c) a.off[c] = h->off[c];
-    a.Px = h->res.Px; a.Py = h->res.Py; a.bxm = h->res.bxm; a.bym = h->res.bym;
-    a.scal = h->c.scal; a.hist = h->c.hist; a.hist_cap = kHistCap;
-    a.n_iter = nb;
-    a.ar = h->res_ar; a.mirror = h->res_mirror;
-    a.tag0 = h->res_epoch + 1u;
-    a.timeout_ticks = h->res_timeout_ticks; a.first_timeout_ticks = h->res_first_timeout_ticks;
-    a.test_drop_wg = h->res_drop_wg;
-    int e = h->dt == MFS_F32 ? vcg_launch_resident<float>(h, a, st) : vcg_launch_resident<double>(h, a, st);
-    if (e) return e;
-    h->res_epoch += 2u * (unsigned)nb;
-    h->c.iter_enq += nb;
-    n -= nb;
-  }
-  return MFS_OK;
-}
-
 int mfs_vcg3d_iterate(mfs_vcg3d* h, int64_t n, mfs_stream stream) {
   MFS_REQUIRE(h && h->c.x && h->is_setup, "engine not bound / set up");
   hipStream_t st = (hipStream_t)stream;
+  const VLoopForm lf = vcg_loop_form(h);
   if (h->jacobi) {
     MFS_REQUIRE(h->diag_ready, "Jacobi loop: mfs_vcg3d_begin has not built the diagonal");
-    const bool vec = core_vec_ok(h->c);
-    // z stored (two streaming kernels, a reduction tail) pays beyond the caches; launch-bound sizes keep the form whose
-    // consumers fold the partial sums themselves (MFS_VISC_JACOBI_Z = 0 / 1 overrides)
-    const int zk = env_int("MFS_VISC_JACOBI_Z", -1);
-    const bool zform = zk < 0 ? (5.0 * (double)h->n * h->c.elt > 100e6) : (zk != 0);
     VcgListScope list(h, st);      // (single-domain solves with lists: the march visits the busy pairs only)
     if (list.err) return list.err;
     for (int64_t i = 0; i < n; ++i) {
-      int e;
-      if (vec && zform) e = h->dt == MFS_F32 ? vcg_jac_iteration_z<float, 4>(h, st) : vcg_jac_iteration_z<double, 2>(h, st);
-      else if (vec) e = h->dt == MFS_F32 ? vcg_jac_iteration<float, 4>(h, st) : vcg_jac_iteration<double, 2>(h, st);
-      else e = h->dt == MFS_F32 ? vcg_jac_iteration<float, 1>(h, st) : vcg_jac_iteration<double, 1>(h, st);
+      const int e = vcg_typed(h, [&](auto t) {
+        typedef decltype(t) T;
+        return lf.kind == kVLoopJacobiZ ? vcg_jac_iteration_z<T, VecOf<T>::N>(h, st)
+               : lf.kind == kVLoopJacobi ? vcg_jac_iteration<T, VecOf<T>::N>(h, st) : vcg_jac_iteration<T, 1>(h, st);
+      });
       if (e) return e;
     }
     return MFS_OK;
   }
-  if (vcg_fuse_ok(h)) {
+  if (lf.kind == kVLoopFused) {
     // Fused loop, 2 launches per iteration:  A | R   A* | R   A* | R ...   A = plain march (iteration 0: d_0 = r_0 is there),
     // A* = march that first forms d_j = r + beta d_{j-1} (into the other buffer of {bound d, d2}) and lets x += alpha d_{j-1}
     // ride along, R = r -= alpha q whose last block closes the iteration (test :606, history, alpha, beta).  x lags one
@@ -2111,12 +1839,9 @@ int mfs_vcg3d_iterate(mfs_vcg3d* h, int64_t n, mfs_stream stream) {
       const int64_t j = h->c.iter_enq;
       void* d_cur = (j & 1) ? h->d2 : h->c.d;
       void* d_prev = (j & 1) ? h->c.d : h->d2;
-      if (j == 0) {
-        if ((e = vcg_apply(h, d_cur, h->c.q, h->c.part_dq, true, false, st, &np))) return e;                    // :589
-      } else {
-        e = h->dt == MFS_F32 ? vcg_march_fused<float>(h, d_prev, d_cur, st, &np) : vcg_march_fused<double>(h, d_prev, d_cur, st, &np);
-        if (e) return e;                                                                                          // :595-597 (x), :609-610, :589
-      }
+      if (j == 0) e = vcg_apply(h, d_cur, h->c.q, h->c.part_dq, true, false, st, &np);                          // :589
+      else e = vcg_apply(h, d_prev, h->c.q, h->c.part_dq, true, false, st, &np, d_cur);      // :595-597 (x), :609-610, :589
+      if (e) return e;
       h->c.n_part_dq = np;
       h->fused_run = true;
       XrTail tl{1, h->c.hist, kHistCap, nullptr, 0, 0};
@@ -2125,23 +1850,23 @@ int mfs_vcg3d_iterate(mfs_vcg3d* h, int64_t n, mfs_stream stream) {
     }
     return MFS_OK;
   }
-  if (vcg_resident_ok(h)) return vcg_iterate_resident(h, n, st);
+  if (lf.kind == kVLoopResident) return vcg_iterate_resident(h, n, st);
   // small problems: both vector phases, the r.r reduction and the bookkeeping in ONE launch whose workgroups exchange
   // their partial sums while resident (k_update_rdx, mfs_cg_core.h): 2 launches per iteration, no reduction tail
-  const bool rdx = core_rdx_ok(h->c) && !h->p2p;
+  const bool rdx = lf.kind == kVLoopMerged;
   // single-domain solves with live-chunk vector phases (vcg_build_live): the march visits only the busy (tile, plane)
   // pairs -- q of an all-air pair is +0 since the initial q = A x and nothing else writes it
   VcgListScope list(h, st);
   if (list.err) return list.err;
   for (int64_t i = 0; i < n; ++i) {
     int e, np = 0;
-    if ((e = vcg_apply(h, h->c.d, h->c.q, h->c.part_dq, true, h->mask_cg != 0, st, &np))) return e;   // :589
+    if ((e = vcg_apply(h, h->c.d, h->c.q, h->c.part_dq, true, false, st, &np))) return e;   // :589
     h->c.n_part_dq = np;
     if (rdx) {
       if ((e = core_update_rdx(h->c, st))) return e;                                  // :592-610
       continue;
     }
-    if (h->split_x) {   // r -= alpha q here, x += alpha d rides in the direction update (8 instead of 9 scalars per DOF)
+    if (lf.split_x) {   // r -= alpha q here, x += alpha d rides in the direction update (8 instead of 9 scalars per DOF)
       if ((e = core_update_xr(h->c, true, st, 1))) return e;                          // :592-601 (r)
       if ((e = core_update_d(h->c, true, st, true))) return e;                        // :595-597 (x), :604-610
     } else {
@@ -2149,27 +1874,6 @@ int mfs_vcg3d_iterate(mfs_vcg3d* h, int64_t n, mfs_stream stream) {
       if ((e = core_update_d(h->c, true, st))) return e;                              // :604-610
     }
   }
-  return MFS_OK;
-}
-
-// what the fused loop owes when it stops after `iters` completed iterations: x += alpha d of the last one, the direction
-// update d_iters = r + beta d_{iters-1} unless it converged (the reference updates d at the end of every non-converged
-// iteration, :609-610), and d brought home to the bound array if it sits in the partner buffer
-static int vcg_home(mfs_vcg3d* h, int64_t iters, bool converged, hipStream_t st) {
-  if (!h->fused_run) return MFS_OK;
-  h->fused_run = false;
-  if (iters < 1) return MFS_OK;
-  void* cur = ((iters - 1) & 1) ? h->d2 : h->c.d;             // holds d_{iters-1}
-  const int grid = core_vec_grid(h->c, true);
-  if (h->dt == MFS_F32) hipLaunchKernelGGL((k_x_axpy<float, 4>), dim3(grid), dim3(kBlock), 0, st, (float*)h->c.x, (const float*)cur, h->n, h->c.scal);
-  else hipLaunchKernelGGL((k_x_axpy<double, 2>), dim3(grid), dim3(kBlock), 0, st, (double*)h->c.x, (const double*)cur, h->n, h->c.scal);
-  MFS_LAUNCH_CHECK();
-  if (!converged) {
-    if (h->dt == MFS_F32) hipLaunchKernelGGL((k_d_axpy<float, 4>), dim3(grid), dim3(kBlock), 0, st, (float*)cur, (const float*)h->c.r, h->n, h->c.scal);
-    else hipLaunchKernelGGL((k_d_axpy<double, 2>), dim3(grid), dim3(kBlock), 0, st, (double*)cur, (const double*)h->c.r, h->n, h->c.scal);
-    MFS_LAUNCH_CHECK();
-  }
-  if (cur != h->c.d) MFS_HIP_TRY(hipMemcpyAsync(h->c.d, cur, (size_t)h->n * h->c.elt, hipMemcpyDeviceToDevice, st));
   return MFS_OK;
 }
 
@@ -2183,7 +1887,7 @@ int mfs_vcg3d_poll(mfs_vcg3d* h, mfs_stream stream, int64_t* iters, int* done, d
   bool taken_back = false;
   if (int e = core_read_scalars(h->c, st, &taken_back)) return e;
   if (taken_back) {
-    if (vcg_resident_ok(h)) h->resident = 0;      // the resident loop did not get its workgroups: launch-per-phase from now on
+    if (vcg_loop_form(h).kind == kVLoopResident) h->resident = 0;      // the resident loop did not get its workgroups: launch-per-phase from now on
     else h->c.rdx = 0;
   }
   return core_poll(h->c, st, iters, done, delta, alpha, beta, !taken_back);
@@ -2198,7 +1902,7 @@ int mfs_vcg3d_solve(mfs_vcg3d* h, double tol, int64_t max_iter, int64_t check_ev
       h->c, &h->last_iters, max_iter, check_every, iters_host, [&] { return mfs_vcg3d_begin(h, tol, stream); },
       [&](int64_t n) { return mfs_vcg3d_iterate(h, n, stream); },
       [&](int64_t* iters, int* done) { return mfs_vcg3d_poll(h, stream, iters, done, nullptr, nullptr, nullptr); },
-      [&](int64_t iters, bool converged) { return vcg_home(h, iters, converged, st); }, [&] { return vcg_resident_ok(h); });
+      [&](int64_t iters, bool converged) { return vcg_home(h, iters, converged, st); }, [&] { return vcg_loop_form(h).kind == kVLoopResident; });
 }
 
 // for callers that drive begin / iterate themselves: settles what the fused loop owes (the last x update, the direction
@@ -2224,7 +1928,7 @@ int mfs_vcg3d_class_census(mfs_vcg3d* h, int64_t counts_host[3], mfs_stream stre
   if (!h->classes_ready) { if (int e = vcg_build_classes(h, (hipStream_t)stream)) return e; }
   counts_host[0] = counts_host[1] = counts_host[2] = 0;
   const int Nx = h->g.N[0], Ny = h->g.N[1], Nz = h->g.N[2], vec = h->dt == MFS_F32 ? 4 : 2;
-  if (Nx < 3 || Ny < 3 || Nz % vec != 0 || Nz < 2 * vec) return MFS_OK;       // no marching kernel, no classes
+  if (!vcg_form(h, nullptr, nullptr, false, false).rows_ok) return MFS_OK;    // no marching kernel, no classes
   unsigned long long* dv = (unsigned long long*)h->part_rz;                   // scratch: 3 words of the Jacobi partials
   hipStream_t st = (hipStream_t)stream;
   MFS_HIP_TRY(hipStreamSynchronize(st));                                      // (diagnostic call: nothing may be using the scratch)
@@ -2258,13 +1962,11 @@ int mfs_vcg3d_sparse_info(mfs_vcg3d* h, mfs_stream stream, int64_t out[4]) {
   MFS_HIP_TRY(hipStreamSynchronize(st));
   out[0] = v;
   out[1] = (h->n + kLiveChunk - 1) / kLiveChunk;
-  if (h->compress && !h->mask_cg && h->classes_ready && h->list_ready) {
+  if (h->compress && h->classes_ready && h->list_ready) {
     MFS_HIP_TRY(hipMemcpyAsync(&v, h->list_count, sizeof(int), hipMemcpyDeviceToHost, st));
     MFS_HIP_TRY(hipStreamSynchronize(st));
-    const int vec = h->dt == MFS_F32 ? 4 : 2;
-    const int ipp = (h->g.N[1] - 2) * (h->g.N[2] / vec);
     out[2] = v;
-    out[3] = (int64_t)((ipp + h->cp.tw_block - 1) / h->cp.tw_block) * (h->g.N[0] - 2);
+    out[3] = vcg_form(h, nullptr, nullptr, false, false).total;      // (the list exists: built for this geometry)
   }
   return MFS_OK;
 }
@@ -2279,10 +1981,7 @@ int mfs_vcg3d_set_fuse(mfs_vcg3d* h, int on) {
 
 // what mfs_vcg3d_iterate will do for the engine as bound: bit 0 fused direction + x update (2 launches per iteration)
 int mfs_vcg3d_loop_info(mfs_vcg3d* h) {
-  if (!h) return 0;
-  if (!h->c.x || !h->is_setup) return h->jacobi ? 4 : 0;
-  if (vcg_resident_ok(h)) return 8;
-  return (vcg_fuse_ok(h) ? 1 : 0) | ((!h->jacobi && !vcg_fuse_ok(h) && core_rdx_ok(h->c) && !h->p2p) ? 2 : 0) | (h->jacobi ? 4 : 0);
+  return h ? vcg_loop_form(h).info : 0;
 }
 
 // 1 / 0: allow the resident small-grid loop (default: on where the grid qualifies; env MFS_VISC_RESIDENT)

@@ -12,8 +12,9 @@ class VcgEngine(FaceCgEngine):
     PREFIX, RANK = "mfs_vcg3d", 3
 
     def apply_kernel(self):
-        """which kernel the CG applies take for the engine as bound: "march" | "tiled" | "scalar" (bit-identical)"""
-        return {2: "march", 1: "tiled", 0: "scalar"}[int(self.lib.mfs_vcg3d_apply_kernel(self.h))]
+        """which kernel the CG applies take for the engine as bound: "march" | "scalar" (bit-identical).  Code 1, the
+        LDS-tiled kernel, is retired: the library returns 2 or 0"""
+        return {2: "march", 0: "scalar"}[int(self.lib.mfs_vcg3d_apply_kernel(self.h))]
 
     def begin(self, tol):
         _lib.check(self.lib.mfs_vcg3d_begin(self.h, float(tol), T.stream()), "mfs_vcg3d_begin")

@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: SQ / TCC counters of the viscosity per-iteration kernels (separate --pmc passes).
-# usage: tools/pmc_visc.sh <tag> <N> [env assignments, e.g. MFS_VISC_TILED=0]
+# usage: tools/pmc_visc.sh <tag> <N> [env assignments, e.g. MFS_VISC_MARCH=0]
 set -e
 TAG=${1:-pmcv}; N=${2:-256}; shift 2 || true
 R=${GRAFT_REPO_ROOT:-/root/repo}

@@ -32,8 +32,10 @@ for _ in range(rounds):
     for val, s in zip((va, vb), engs):
         t0 = time.perf_counter(); s._engine.iterate(iters); torch.cuda.synchronize()
         res[val].append(round((time.perf_counter() - t0) / iters * 1e6, 2))
-# knobs that the library reads per launch: the SAME engine (the first) with the variable toggled between loops --
-# no placement difference at all (at 256^3 the first-created solver of a process runs ~6 % faster than the second)
+# the SAME engine (the first) with the variable toggled between loops -- no placement difference at all (at 256^3 the
+# first-created solver of a process runs ~6 % faster than the second).  Every viscosity knob is read once, at engine
+# creation, so for those this section times one configuration twice: it measures the noise floor, not the knob; it
+# compares something only for variables the library reads per launch (none of the MFS_VISC_* ones)
 same = {va: [], vb: []}
 for _ in range(rounds):
     for val in (va, vb):

@@ -1,6 +1,7 @@
-"""GPU: time the viscosity CG's operator launch alone (mfs_vcg3d_phase_apply: the per-iteration kernel + the boundary
-slabs launch) on the direction vector of a begun solve.  usage: python tools/visc_apply_probe.py [N] [dtype] [reps]
-Environment knobs of csrc/mfs_visc.hip apply (MFS_VISC_XCD, MFS_VISC_TILED, ...); MFS_PROBE_LIB = another build of the library."""
+"""GPU: time the viscosity CG's operator launch alone (mfs_vcg3d_phase_apply: the per-iteration kernel, boundary slabs
+included) on the direction vector of a begun solve.  usage: python tools/visc_apply_probe.py [N] [dtype] [reps]
+Environment knobs of csrc/mfs_visc.hip apply, read at engine creation (MFS_VISC_MARCH, MFS_VISC_MARCH_BLOCK, MFS_VISC_XCD,
+...); MFS_PROBE_LIB = another build of the library."""
 import json, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(REPO, "python-fluid-simulation_amd"), REPO]
