@@ -848,6 +848,47 @@ int mfs_seed_fill3d(const int64_t shape[3], const double origin[3], double spaci
                     const void* masks, const void* offsets, void* positions, int pos_dt, void* sites, int64_t capacity,
                     mfs_stream stream);
 
+/* ------------------------------------------------------------------------- */
+/* Ray-marched images (csrc/mfs_render.hip; DESIGN.md "Rendering")             */
+/* ------------------------------------------------------------------------- */
+/* No reference counterpart: the reference hands its points to a notebook widget.  Additions: the ABI version stays.
+ * Shapes: 1 to 16, described by the *_host arrays of mfs_seed_count3d (HOST memory, read before the launch).  Shape i at a
+ * world point x is sampled at the body point R^T (x - T) exactly as there, but shows only inside its own box: with
+ * u_a = (xb_a - origin_a) / spacing, the value is the trilinear sample if 0 <= u_a <= n_a - 1 on all axes and +inf
+ * otherwise.  F(x) = min over the shapes, taken with a strict < from +inf: the id is the first shape that attains it and a
+ * NaN sample is passed over.
+ * camera: 14 HOST doubles, eye[3], f[3], r[3], u[3], half_w, half_h (an orthonormal frame; half the image plane's extents
+ * at unit distance, or in world units when `ortho`).  Pixel (i, j), row i from the top: sx = ((j + 0.5) * (2 / W) - 1) *
+ * half_w, sy = (1 - (i + 0.5) * (2 / H)) * half_h; perspective: o = eye, v = (f + sx r) + sy u, d = v / |v|; orthographic:
+ * o = (eye + sx r) + sy u, d = f.  width, height in 1 .. 16384.
+ * March: sample k of num_steps (1 .. 65536) is at t_k = near + k * step, x_k = o + t_k d.  The hit is the smallest k with
+ * F(x_k) < 0; with a = F(x_{k-1}), b = F(x_k): depth = (t_k - step) + step * (a / (a - b)) if k > 0 and a is finite, else
+ * t_k.  The normal is the hit shape's central difference over +-0.5 spacing along the world axes at o + depth d, sampled
+ * as mfs_seed_count3d samples (clamp plus distance outside the box) and normalised; -d where its length is 0 or not finite.
+ * All arithmetic on the ray is float64, every operation rounded on its own.
+ * Outputs (DEVICE, height x width, C order): depth float64 (+inf at a miss), normal 3 x float32 (0 at a miss), shape_id
+ * int32 (-1), steps int32 (the hit k; -1); evals (may be null) int32, the shape samples the pixel's lane evaluated in
+ * its walk.
+ * bricks_host[i]: DEVICE array of _brick_count3d(extents) float64 from _bricks3d, C order over ceil((n - 1) / 8) bricks
+ * per axis: the minimum over the nodes 8 b .. min(8 b + 8, n - 1) of brick b, -inf if one of them is NaN.  With skip != 0
+ * the march passes over samples of a shape that lie before the ray's entry into the shape's box, after its exit, or in
+ * a brick whose minimum is > 0; the outputs, evals apart, are the same bits as with skip == 0 (bricks_host may then be
+ * null), which evaluates every shape at every sample up to the hit.
+ * _shade3d: rgb (DEVICE, height x width x 3 uint8) = floor(255 c + 0.5), c = albedo[id] * (0.25 + 0.75 * max(0, n . l)),
+ * l = -d of the pixel's ray, or light_host (3 HOST doubles, the unit vector towards the light) when not null;
+ * albedo_host: num_colors (1 .. 16) x 3 HOST doubles; background_host: 3 HOST ints in 0 .. 255, stored where id < 0 or
+ * id >= num_colors.  near / step / num_steps play no part in it.                                                   */
+int64_t mfs_render_brick_count3d(const int64_t extents[3]);
+int mfs_render_bricks3d(const void* volume, int dtype, const int64_t extents[3], void* bricks, mfs_stream stream);
+int mfs_render_march3d(const double* camera, int ortho, int64_t width, int64_t height, double near, double step,
+                       int64_t num_steps, int64_t num_shapes, const void* const* volumes_host, const int* dtypes_host,
+                       const int64_t* extents_host, const double* origins_host, const double* spacings_host,
+                       const double* poses_host, const void* const* bricks_host, int skip, void* depth, void* normal,
+                       void* shape_id, void* steps, void* evals, mfs_stream stream);
+int mfs_render_shade3d(const double* camera, int ortho, int64_t width, int64_t height, const void* normal,
+                       const void* shape_id, int64_t num_colors, const double* albedo_host, const int* background_host,
+                       const double* light_host, void* rgb, mfs_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

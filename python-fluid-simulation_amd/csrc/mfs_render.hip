@@ -1,0 +1,506 @@
+// mfs_render.hip -- ray-marched images of level-set volumes on gfx950 (no reference counterpart):
+//   k_render_bricks  one workgroup per brick of 8 x 8 x 8 cells (9^3 nodes, clipped at the volume's end): its minimum,
+//                    -inf when it holds a NaN; wave reduction, no atomics
+//   k_render_march   one lane per pixel, one wave per 8 x 8 pixel tile: walks the samples t_k = near + k * step of its ray,
+//                    stops at the first with min over the shapes < 0, refines by one secant step, takes the normal
+//   k_render_shade   Lambert from the normals and shape ids, one lane per pixel
+// Every shape is a sampled signed field under a rigid pose, as in mfs_seed.hip; the arithmetic on the ray is float64 with
+// contraction off and is restated in numpy operation by operation (tests/render_numpy.py).
+#include <math.h>
+
+#include "mfs_common.h"
+
+namespace mfs {
+
+constexpr int kRenderBlock = 256;          // threads per workgroup: four waves, each an 8 x 8 pixel tile of a 16 x 16 block
+constexpr int kRenderTile = 16;            // pixels per workgroup edge
+constexpr int kMaxRenderShapes = 16;
+constexpr int kBrick = 8;                  // cells per brick edge
+constexpr int kBrickNodes = (kBrick + 1) * (kBrick + 1) * (kBrick + 1);
+// Node units by which a box is widened and a brick narrowed before a skip is computed from it.  The skips work on the line
+// u0 + t du in a shape's node coordinates, the samples on x_k = o + t_k d taken to the body frame: the two differ by a few
+// roundings of coordinates below 2^40 nodes, far less than this.
+constexpr double kSkipMargin = 1e-3;
+
+struct RenderCamera {
+  double eye[3], f[3], r[3], u[3];
+  double half_w, half_h;
+  double near, step;
+  int ortho, W, H, K;
+};
+
+struct RenderShapes {                      // by value in the launch
+  const void* vol[kMaxRenderShapes];
+  const double* brick[kMaxRenderShapes];
+  int dt[kMaxRenderShapes];
+  int n[kMaxRenderShapes][3];
+  int nb[kMaxRenderShapes][3];             // bricks along each axis: ceil((n - 1) / 8)
+  double org[kMaxRenderShapes][3];
+  double h[kMaxRenderShapes];
+  double R[kMaxRenderShapes][3][3];
+  double T[kMaxRenderShapes][3];
+};
+
+struct RenderPalette {
+  double albedo[kMaxRenderShapes][3];
+  double light[3];
+  int background[3];
+  int n, has_light;
+};
+
+#pragma clang fp contract(off)
+
+// mfs_seed.hip's seed_sample, operation by operation: shape i at the world point x is its volume sampled trilinearly at
+// R^T (x - T); outside the box: the sample at the clamped point plus the distance to the box.  inside: 0 <= u <= n - 1 on
+// all three axes, u the node coordinate; cell: the clamped cell the loads came from.  Every load is in bounds whatever x.
+__device__ __forceinline__ double render_sample(const RenderShapes& S, int i, const double x[3], bool* inside, int cell[3]) {
+  const double d[3] = {x[0] - S.T[i][0], x[1] - S.T[i][1], x[2] - S.T[i][2]};
+  int64_t c[3];
+  double f[3], e[3];
+  bool in = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double xb = (S.R[i][0][k] * d[0] + S.R[i][1][k] * d[1]) + S.R[i][2][k] * d[2];
+    const double t = (xb - S.org[i][k]) / S.h[i];
+    const double hi = (double)(S.n[i][k] - 1);
+    in = in && t >= 0.0 && t <= hi;
+    const double tc = fmin(fmax(t, 0.0), hi);
+    int ci = (int)floor(tc);
+    if (ci > S.n[i][k] - 2) ci = S.n[i][k] - 2;
+    if (ci < 0) ci = 0;                               // never taken for a finite point; keeps the loads in bounds regardless
+    c[k] = ci;
+    cell[k] = ci;
+    f[k] = tc - (double)ci;
+    e[k] = (t - tc) * S.h[i];
+  }
+  *inside = in;
+  const int64_t s0 = (int64_t)S.n[i][1] * S.n[i][2], s1 = S.n[i][2];
+  const int64_t p = c[0] * s0 + c[1] * s1 + c[2];
+  const void* v = S.vol[i];
+  const int dt = S.dt[i];
+  const double v000 = ldx(v, dt, p), v001 = ldx(v, dt, p + 1), v010 = ldx(v, dt, p + s1), v011 = ldx(v, dt, p + s1 + 1);
+  const double v100 = ldx(v, dt, p + s0), v101 = ldx(v, dt, p + s0 + 1), v110 = ldx(v, dt, p + s0 + s1),
+               v111 = ldx(v, dt, p + s0 + s1 + 1);
+  const double g0 = 1.0 - f[0], g1 = 1.0 - f[1], g2 = 1.0 - f[2];
+  const double c00 = v000 * g2 + v001 * f[2], c01 = v010 * g2 + v011 * f[2];
+  const double c10 = v100 * g2 + v101 * f[2], c11 = v110 * g2 + v111 * f[2];
+  const double c0 = c00 * g1 + c01 * f[1], c1 = c10 * g1 + c11 * f[1];
+  const double dist = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+  return (c0 * g0 + c1 * f[0]) + dist;
+}
+
+// the render rule: a shape shows inside its own box only
+__device__ __forceinline__ double render_value(const RenderShapes& S, int i, const double x[3]) {
+  bool inside;
+  int cell[3];
+  const double v = render_sample(S, i, x, &inside, cell);
+  return inside ? v : INFINITY;
+}
+
+// F(x) = min over the shapes, taken with a strict < from +inf: the first shape that attains it; a NaN is passed over
+__device__ __forceinline__ double render_scene(const RenderShapes& S, int n, const double x[3]) {
+  double best = INFINITY;
+  for (int i = 0; i < n; ++i) {
+    const double v = render_value(S, i, x);
+    if (v < best) best = v;
+  }
+  return best;
+}
+
+// pixel (i, j), row i from the top -> origin and unit direction of its ray
+__device__ __forceinline__ void render_ray(const RenderCamera& C, int i, int j, double o[3], double d[3]) {
+  const double sx = (((double)j + 0.5) * (2.0 / (double)C.W) - 1.0) * C.half_w;
+  const double sy = (1.0 - ((double)i + 0.5) * (2.0 / (double)C.H)) * C.half_h;
+  if (C.ortho) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      o[a] = (C.eye[a] + sx * C.r[a]) + sy * C.u[a];
+      d[a] = C.f[a];
+    }
+  } else {
+    double v[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      o[a] = C.eye[a];
+      v[a] = (C.f[a] + sx * C.r[a]) + sy * C.u[a];
+    }
+    const double len = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) d[a] = v[a] / len;
+  }
+}
+
+// ---- the skips.  Nothing below enters a result: it only decides which samples of which shape are not evaluated, and every
+// decision errs towards evaluating (DESIGN.md 4.16 has the argument).
+
+// the ray in shape i's node coordinates: u(t) = u0 + t du
+__device__ __forceinline__ void render_ray_nodes(const RenderShapes& S, int i, const double o[3], const double d[3],
+                                                 double u0[3], double du[3]) {
+  const double e[3] = {o[0] - S.T[i][0], o[1] - S.T[i][1], o[2] - S.T[i][2]};
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    u0[k] = (((S.R[i][0][k] * e[0] + S.R[i][1][k] * e[1]) + S.R[i][2][k] * e[2]) - S.org[i][k]) / S.h[i];
+    du[k] = ((S.R[i][0][k] * d[0] + S.R[i][1][k] * d[1]) + S.R[i][2][k] * d[2]) / S.h[i];
+  }
+}
+
+// the parameter interval [tin, tout] over which the line lies in the box [lo, hi]; false if it is empty
+__device__ __forceinline__ bool render_slab(const double u0[3], const double du[3], const double lo[3], const double hi[3],
+                                            double* tin, double* tout) {
+  double a = -INFINITY, b = INFINITY;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (du[k] == 0.0) {
+      if (!(u0[k] >= lo[k] && u0[k] <= hi[k])) return false;
+    } else {
+      const double t1 = (lo[k] - u0[k]) / du[k], t2 = (hi[k] - u0[k]) / du[k];
+      a = fmax(a, fmin(t1, t2));
+      b = fmin(b, fmax(t1, t2));
+    }
+  }
+  *tin = a;
+  *tout = b;
+  return a <= b;
+}
+
+// floor((t - near) / step) + shift as a sample index, held in [lo, K]
+__device__ __forceinline__ int render_index(const RenderCamera& C, double t, double shift, int lo) {
+  double q = floor((t - C.near) / C.step) + shift;
+  if (!(q > (double)lo)) return lo;                   // also a NaN
+  if (q > (double)C.K) return C.K;
+  return (int)q;
+}
+
+// The smallest sample index >= kmin of shape i that has to be evaluated, when all that is known is the shape's box: the
+// samples before the ray enters the box widened by the margin are outside the box itself, and so are all of them if the
+// ray misses the widened box or has left it before sample kmin.  One sample is given away at the entry.
+__device__ __forceinline__ int render_next_outside(const RenderCamera& C, const RenderShapes& S, int i, const double o[3],
+                                                   const double d[3], int kmin) {
+  double u0[3], du[3], lo[3], hi[3], tin, tout;
+  render_ray_nodes(S, i, o, d, u0, du);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    lo[k] = -kSkipMargin;
+    hi[k] = (double)(S.n[i][k] - 1) + kSkipMargin;
+  }
+  if (!render_slab(u0, du, lo, hi, &tin, &tout)) return C.K;
+  if (tout < C.near + (double)kmin * C.step) return C.K;
+  return render_index(C, tin, -1.0, kmin);
+}
+
+// Sample k of shape i lies in the brick of `cell`, whose minimum is > 0: the samples up to the ray's exit from the brick
+// narrowed by the margin fall into cells of that brick, where a trilinear sample, a combination of the cell's nodes with
+// weights in [0, 1], cannot be negative.  Returns the first index after them (k + 1 if sample k itself is not in the
+// narrowed brick); one sample is given away at the exit.
+__device__ __forceinline__ int render_next_brick(const RenderCamera& C, const RenderShapes& S, int i, const double o[3],
+                                                 const double d[3], int k, const int cell[3]) {
+  double u0[3], du[3], lo[3], hi[3], tin, tout;
+  render_ray_nodes(S, i, o, d, u0, du);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int b = cell[a] / kBrick;
+    const int end = min(kBrick * b + kBrick, S.n[i][a] - 1);
+    lo[a] = (double)(kBrick * b) + kSkipMargin;
+    hi[a] = (double)end - kSkipMargin;
+  }
+  if (!render_slab(u0, du, lo, hi, &tin, &tout)) return k + 1;
+  if (!(tin <= C.near + (double)k * C.step)) return k + 1;
+  return render_index(C, tout, 0.0, k + 1);
+}
+
+__global__ void __launch_bounds__(kRenderBlock)
+k_render_march(RenderCamera C, RenderShapes S, int n, int skip, double* __restrict__ depth, float* __restrict__ normal,
+               int* __restrict__ shape_id, int* __restrict__ steps, int* __restrict__ evals) {
+  // per lane and shape: the next sample index at which the shape has to be evaluated.  Each lane reads and writes its own
+  // column only: no barrier.
+  __shared__ int s_next[kMaxRenderShapes][kRenderBlock];
+  const int tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
+  const int j = (int)blockIdx.x * kRenderTile + (wave & 1) * 8 + (lane & 7);
+  const int i = (int)blockIdx.y * kRenderTile + (wave >> 1) * 8 + (lane >> 3);
+  if (i >= C.H || j >= C.W) return;
+  double o[3], d[3];
+  render_ray(C, i, j, o, d);
+
+  int k = C.K;
+  for (int s = 0; s < n; ++s) {
+    const int nx = skip ? render_next_outside(C, S, s, o, d, 0) : 0;
+    s_next[s][tid] = nx;
+    k = min(k, nx);
+  }
+  int count = 0, id = -1;
+  double b = INFINITY;
+  bool hit = false;
+  while (k < C.K) {                                   // k grows by at least 1 per pass: at most K passes
+    const double t = C.near + (double)k * C.step;
+    const double x[3] = {o[0] + t * d[0], o[1] + t * d[1], o[2] + t * d[2]};
+    double best = INFINITY;
+    int arg = -1, knext = C.K;
+    for (int s = 0; s < n; ++s) {
+      int nx = s_next[s][tid];
+      if (nx <= k) {
+        bool inside;
+        int cell[3];
+        double v = render_sample(S, s, x, &inside, cell);
+        ++count;
+        nx = k + 1;
+        if (!inside) {
+          v = INFINITY;
+          if (skip) nx = render_next_outside(C, S, s, o, d, k + 1);
+        } else if (skip && !(v < 0.0)) {
+          const double m = S.brick[s][((int64_t)(cell[0] / kBrick) * S.nb[s][1] + cell[1] / kBrick) * S.nb[s][2] + cell[2] / kBrick];
+          if (m > 0.0) nx = render_next_brick(C, S, s, o, d, k, cell);
+        }
+        s_next[s][tid] = nx;
+        if (v < best) {
+          best = v;
+          arg = s;
+        }
+      }
+      knext = min(knext, nx);
+    }
+    if (best < 0.0) {
+      hit = true;
+      b = best;
+      id = arg;
+      break;
+    }
+    k = knext;
+  }
+
+  const int64_t p = (int64_t)i * C.W + j;
+  if (evals) evals[p] = count;
+  if (!hit) {
+    depth[p] = INFINITY;
+    normal[3 * p] = normal[3 * p + 1] = normal[3 * p + 2] = 0.0f;
+    shape_id[p] = -1;
+    steps[p] = -1;
+    return;
+  }
+  // the secant needs the true F(x_{k-1}): a skip may have passed over that sample, so it is evaluated here, in full
+  const double tk = C.near + (double)k * C.step;
+  double dep = tk;
+  if (k > 0) {
+    const double tp = C.near + (double)(k - 1) * C.step;
+    const double xp[3] = {o[0] + tp * d[0], o[1] + tp * d[1], o[2] + tp * d[2]};
+    const double a = render_scene(S, n, xp);
+    if (a < INFINITY && a > -INFINITY) dep = (tk - C.step) + C.step * (a / (a - b));
+  }
+  const double xh[3] = {o[0] + dep * d[0], o[1] + dep * d[1], o[2] + dep * d[2]};
+  const double hh = 0.5 * S.h[id];
+  double g[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    double xa[3] = {xh[0], xh[1], xh[2]}, xb[3] = {xh[0], xh[1], xh[2]};
+    xa[a] = xh[a] + hh;
+    xb[a] = xh[a] - hh;
+    bool inside;
+    int cell[3];
+    const double va = render_sample(S, id, xa, &inside, cell);
+    const double vb = render_sample(S, id, xb, &inside, cell);
+    g[a] = va - vb;
+  }
+  const double len = sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
+  const bool ok = len > 0.0 && len < INFINITY;
+  depth[p] = dep;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) normal[3 * p + a] = ok ? (float)(g[a] / len) : (float)(-d[a]);
+  shape_id[p] = id;
+  steps[p] = k;
+}
+
+// wave minimum in every lane (the tree of wave_sum); all 64 lanes active, no NaN among the operands
+__device__ __forceinline__ double wave_min(double v) {
+  v = fmin(v, dpp_f64<0xB1>(v));
+  v = fmin(v, dpp_f64<0x4E>(v));
+  v = fmin(v, dpp_f64<0x124>(v));
+  v = fmin(v, dpp_f64<0x128>(v));
+  return fmin(fmin(readlane_f64(v, 0), readlane_f64(v, 16)), fmin(readlane_f64(v, 32), readlane_f64(v, 48)));
+}
+
+__global__ void __launch_bounds__(kRenderBlock)
+k_render_bricks(const void* __restrict__ vol, int dt, int n0, int n1, int n2, int nb1, int nb2, double* __restrict__ out) {
+  __shared__ double s_part[kRenderBlock / kWave];
+  const int tid = threadIdx.x;
+  const int b2 = (int)(blockIdx.x % (unsigned)nb2), b1 = (int)((blockIdx.x / (unsigned)nb2) % (unsigned)nb1),
+            b0 = (int)(blockIdx.x / (unsigned)nb2 / (unsigned)nb1);
+  double m = INFINITY;
+  for (int q = tid; q < kBrickNodes; q += kRenderBlock) {
+    const int i0 = kBrick * b0 + q / 81, i1 = kBrick * b1 + (q / 9) % 9, i2 = kBrick * b2 + q % 9;
+    if (i0 < n0 && i1 < n1 && i2 < n2) {
+      double v = ldx(vol, dt, ((int64_t)i0 * n1 + i1) * n2 + i2);
+      if (v != v) v = -INFINITY;
+      m = fmin(m, v);
+    }
+  }
+  m = wave_min(m);
+  if ((tid & (kWave - 1)) == 0) s_part[tid / kWave] = m;
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int w = 1; w < kRenderBlock / kWave; ++w) m = fmin(m, s_part[w]);
+    out[blockIdx.x] = m;
+  }
+}
+
+// albedo_id * (0.25 + 0.75 * max(0, n . l)), l = -d (a headlight) or the given direction; floor(255 c + 0.5)
+__global__ void __launch_bounds__(kRenderBlock)
+k_render_shade(RenderCamera C, RenderPalette P, const float* __restrict__ normal, const int* __restrict__ shape_id,
+               unsigned char* __restrict__ rgb) {
+  const int64_t p = (int64_t)blockIdx.x * kRenderBlock + threadIdx.x;
+  if (p >= (int64_t)C.W * C.H) return;
+  const int id = shape_id[p];
+  if (id < 0 || id >= P.n) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) rgb[3 * p + a] = (unsigned char)P.background[a];
+    return;
+  }
+  double l[3] = {P.light[0], P.light[1], P.light[2]};
+  if (!P.has_light) {
+    double o[3], d[3];
+    render_ray(C, (int)(p / C.W), (int)(p % C.W), o, d);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) l[a] = -d[a];
+  }
+  const double nl = ((double)normal[3 * p] * l[0] + (double)normal[3 * p + 1] * l[1]) + (double)normal[3 * p + 2] * l[2];
+  const double lam = fmax(0.0, nl);
+  const double w = 0.25 + 0.75 * lam;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double c = P.albedo[id][a] * w;
+    double q = floor(255.0 * c + 0.5);
+    q = fmin(fmax(q, 0.0), 255.0);                    // fmax drops a NaN
+    rgb[3 * p + a] = (unsigned char)(int)q;
+  }
+}
+
+static int fill_render_camera(RenderCamera* C, const double* camera, int ortho, int64_t width, int64_t height, double near,
+                              double step, int64_t num_steps) {
+  MFS_REQUIRE(camera, "null camera");
+  MFS_REQUIRE(width >= 1 && width <= 16384 && height >= 1 && height <= 16384, "image extents must be in 1 .. 16384");
+  MFS_REQUIRE(num_steps >= 1 && num_steps <= 65536, "number of steps must be in 1 .. 65536");
+  MFS_REQUIRE(step > 0 && isfinite(step) && isfinite(near), "near must be finite and step positive");
+  for (int k = 0; k < 14; ++k) MFS_REQUIRE(isfinite(camera[k]), "camera must be finite");
+  MFS_REQUIRE(camera[12] > 0 && camera[13] > 0, "camera half extents must be positive");
+  const double* f = camera + 3;
+  MFS_REQUIRE((f[0] * f[0] + f[1] * f[1]) + f[2] * f[2] > 0.25, "degenerate view direction");
+  for (int k = 0; k < 3; ++k) {
+    C->eye[k] = camera[k];
+    C->f[k] = camera[3 + k];
+    C->r[k] = camera[6 + k];
+    C->u[k] = camera[9 + k];
+  }
+  C->half_w = camera[12];
+  C->half_h = camera[13];
+  C->near = near;
+  C->step = step;
+  C->ortho = ortho ? 1 : 0;
+  C->W = (int)width;
+  C->H = (int)height;
+  C->K = (int)num_steps;
+  return MFS_OK;
+}
+
+static bool render_extents_ok(const int64_t* e) {
+  return e[0] >= 2 && e[1] >= 2 && e[2] >= 2 && e[0] < ((int64_t)1 << 31) / e[1] / e[2];
+}
+
+}  // namespace mfs
+
+using namespace mfs;
+
+extern "C" {
+
+int64_t mfs_render_brick_count3d(const int64_t extents[3]) {
+  if (!extents || !render_extents_ok(extents)) return 0;
+  return ((extents[0] - 2) / kBrick + 1) * ((extents[1] - 2) / kBrick + 1) * ((extents[2] - 2) / kBrick + 1);
+}
+
+int mfs_render_bricks3d(const void* volume, int dtype, const int64_t extents[3], void* bricks, mfs_stream stream) {
+  MFS_REQUIRE(volume && extents && bricks, "null volume / extents / bricks");
+  MFS_REQUIRE(dtype_ok(dtype), "dtype");
+  MFS_REQUIRE(render_extents_ok(extents), "volume extents must be >= 2, fewer than 2^31 nodes");
+  const int nb1 = (int)((extents[1] - 2) / kBrick + 1), nb2 = (int)((extents[2] - 2) / kBrick + 1);
+  const int64_t blocks = mfs_render_brick_count3d(extents);
+  hipLaunchKernelGGL(k_render_bricks, dim3((unsigned)blocks), dim3(kRenderBlock), 0, (hipStream_t)stream, volume, dtype,
+                     (int)extents[0], (int)extents[1], (int)extents[2], nb1, nb2, (double*)bricks);
+  MFS_LAUNCH_CHECK();
+  return MFS_OK;
+}
+
+int mfs_render_march3d(const double* camera, int ortho, int64_t width, int64_t height, double near, double step,
+                       int64_t num_steps, int64_t num_shapes, const void* const* volumes_host, const int* dtypes_host,
+                       const int64_t* extents_host, const double* origins_host, const double* spacings_host,
+                       const double* poses_host, const void* const* bricks_host, int skip, void* depth, void* normal,
+                       void* shape_id, void* steps, void* evals, mfs_stream stream) {
+  RenderCamera C;
+  if (int st = fill_render_camera(&C, camera, ortho, width, height, near, step, num_steps)) return st;
+  MFS_REQUIRE(num_shapes >= 1 && num_shapes <= kMaxRenderShapes, "1 to 16 shapes per scene");
+  MFS_REQUIRE(volumes_host && dtypes_host && extents_host && origins_host && spacings_host && poses_host,
+              "null shape description");
+  MFS_REQUIRE(!skip || bricks_host, "null brick grids");
+  MFS_REQUIRE(depth && normal && shape_id && steps, "null output");
+  const int m = (int)num_shapes;
+  RenderShapes S;
+  memset(&S, 0, sizeof(S));
+  for (int i = 0; i < m; ++i) {
+    MFS_REQUIRE(volumes_host[i], "null shape volume");
+    MFS_REQUIRE(!skip || bricks_host[i], "null brick grid");
+    MFS_REQUIRE(dtype_ok(dtypes_host[i]), "dtype");
+    MFS_REQUIRE(spacings_host[i] > 0 && isfinite(spacings_host[i]), "shape volume spacing must be positive");
+    const int64_t* e = extents_host + 3 * i;
+    MFS_REQUIRE(render_extents_ok(e), "shape volume extents must be >= 2, fewer than 2^31 nodes");
+    S.vol[i] = volumes_host[i];
+    S.brick[i] = skip ? (const double*)bricks_host[i] : nullptr;
+    S.dt[i] = dtypes_host[i];
+    S.h[i] = spacings_host[i];
+    for (int k = 0; k < 3; ++k) {
+      S.n[i][k] = (int)e[k];
+      S.nb[i][k] = (int)((e[k] - 2) / kBrick + 1);
+      MFS_REQUIRE(isfinite(origins_host[3 * i + k]) && isfinite(poses_host[12 * i + 9 + k]), "shape origin / translation");
+      S.org[i][k] = origins_host[3 * i + k];
+      S.T[i][k] = poses_host[12 * i + 9 + k];
+      for (int c = 0; c < 3; ++c) {
+        MFS_REQUIRE(isfinite(poses_host[12 * i + 3 * k + c]), "shape rotation");
+        S.R[i][k][c] = poses_host[12 * i + 3 * k + c];
+      }
+    }
+  }
+  const dim3 grid((unsigned)((C.W + kRenderTile - 1) / kRenderTile), (unsigned)((C.H + kRenderTile - 1) / kRenderTile));
+  hipLaunchKernelGGL(k_render_march, grid, dim3(kRenderBlock), 0, (hipStream_t)stream, C, S, m, skip ? 1 : 0, (double*)depth,
+                     (float*)normal, (int*)shape_id, (int*)steps, (int*)evals);
+  MFS_LAUNCH_CHECK();
+  return MFS_OK;
+}
+
+int mfs_render_shade3d(const double* camera, int ortho, int64_t width, int64_t height, const void* normal,
+                       const void* shape_id, int64_t num_colors, const double* albedo_host, const int* background_host,
+                       const double* light_host, void* rgb, mfs_stream stream) {
+  RenderCamera C;
+  if (int st = fill_render_camera(&C, camera, ortho, width, height, 0.0, 1.0, 1)) return st;
+  MFS_REQUIRE(normal && shape_id && rgb, "null normal / shape_id / rgb");
+  MFS_REQUIRE(num_colors >= 1 && num_colors <= kMaxRenderShapes, "1 to 16 colours");
+  MFS_REQUIRE(albedo_host && background_host, "null albedo / background");
+  RenderPalette P;
+  memset(&P, 0, sizeof(P));
+  P.n = (int)num_colors;
+  for (int k = 0; k < 3 * P.n; ++k) {
+    MFS_REQUIRE(isfinite(albedo_host[k]), "albedo must be finite");
+    P.albedo[k / 3][k % 3] = albedo_host[k];
+  }
+  for (int k = 0; k < 3; ++k) {
+    MFS_REQUIRE(background_host[k] >= 0 && background_host[k] <= 255, "background must be in 0 .. 255");
+    P.background[k] = background_host[k];
+    if (light_host) {
+      MFS_REQUIRE(isfinite(light_host[k]), "light must be finite");
+      P.light[k] = light_host[k];
+    }
+  }
+  P.has_light = light_host ? 1 : 0;
+  const int64_t pixels = (int64_t)C.W * C.H;
+  hipLaunchKernelGGL(k_render_shade, dim3((unsigned)((pixels + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0,
+                     (hipStream_t)stream, C, P, (const float*)normal, (const int*)shape_id, (unsigned char*)rgb);
+  MFS_LAUNCH_CHECK();
+  return MFS_OK;
+}
+
+}  // extern "C"

@@ -244,6 +244,11 @@ SIGNATURES = {
     "mfs_seed_count3d": (_i, [_pi64, _pd, _d, _d, C.c_uint64, _i64, _i64, C.POINTER(_p), _pint, _pi64, _pd, _pd, _pd, _d,
                               _p, _p, _p]),
     "mfs_seed_fill3d": (_i, [_pi64, _pd, _d, _d, C.c_uint64, _p, _p, _p, _i, _p, _i64, _p]),
+    "mfs_render_brick_count3d": (_i64, [_pi64]),
+    "mfs_render_bricks3d": (_i, [_p, _i, _pi64, _p, _p]),
+    "mfs_render_march3d": (_i, [_pd, _i, _i64, _i64, _d, _d, _i64, _i64, C.POINTER(_p), _pint, _pi64, _pd, _pd, _pd,
+                                C.POINTER(_p), _i, _p, _p, _p, _p, _p, _p]),
+    "mfs_render_shade3d": (_i, [_pd, _i, _i64, _i64, _p, _p, _i64, _pd, _pint, _pd, _p, _p]),
 }
 
 _lib = None

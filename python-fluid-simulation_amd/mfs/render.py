@@ -1,0 +1,356 @@
+"""Ray-marched images of the liquid and the solids on the GPU (csrc/mfs_render.hip; DESIGN.md "Rendering"): a node with
+no display gets a frame of a run as an array of bytes, and `save_png` writes it with the standard library alone.
+
+Everything visible is a sampled signed field under a rigid pose -- a `SkinField`, `solid_levelset.phi`, a `MeshBody`'s
+`MeshSDF`: the shapes of `mfs.seed` (`Shape`, `as_shape`).  `Scene(shapes)` builds a grid of brick minima per shape;
+`scene.render(camera)` walks every pixel's ray in float64 at a fixed step, stops at the first sample where the minimum
+over the shapes is negative, refines it by one secant step and takes the hit shape's normal: a `RenderResult` of depth,
+normal, shape id and step index.  `shade` turns that into Lambert bytes.  The bricks only save work: with skip=False the
+marcher visits every sample of every shape and returns the same bits.  tests/render_numpy.py restates the contract.
+
+    cam = render.Camera(eye=(0.9, 0.8, 1.1), target=(0, 0.3, 0), width=1920, height=1080)
+    rgb = sim.render(cam)                                   # NotebookSimulation: the skin and the solid level set
+    render.save_png("frame.png", rgb)
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+import struct
+import zlib
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import seed as _seed
+from . import tensors as T
+
+MAX_SHAPES = 16                         # the shapes' descriptions travel by value in the launch
+MAX_EXTENT = 16384                      # pixels per image axis
+MAX_STEPS = 65536                       # samples per ray
+TILE = 16                               # pixels per workgroup edge: four waves, each a tile of 8 x 8
+BRICK = 8                               # cells per brick edge
+
+
+def _unit(v):
+    return v / np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+
+
+def check_sizes(width, height, num_steps=1):
+    """(pixels, workgroups) of an image, after the checks that need no device"""
+    width, height, num_steps = int(width), int(height), int(num_steps)
+    if not (1 <= width <= MAX_EXTENT and 1 <= height <= MAX_EXTENT):
+        raise ValueError(f"image {width} x {height}: width and height must be in 1 .. {MAX_EXTENT}")
+    if not (1 <= num_steps <= MAX_STEPS):
+        raise ValueError(f"{num_steps} samples per ray: expected 1 .. {MAX_STEPS}; use a larger step or a tighter near / far")
+    return width * height, ((width + TILE - 1) // TILE) * ((height + TILE - 1) // TILE)
+
+
+class Camera:
+    """A pinhole (fov: the vertical field of view in degrees) or, with ortho_height (the image plane's height in world
+    units), an orthographic camera at `eye` looking at `target`.  near / far: the marched interval of the ray parameter
+    (distance along the ray); None: taken at each render from the shapes' posed boxes, one step wider, and reported in
+    the result.  Row 0 of an image is its top."""
+
+    def __init__(self, eye, target, up=(0.0, 1.0, 0.0), fov=40.0, ortho_height=None, width=640, height=480, near=None,
+                 far=None):
+        self.eye, self.target, self.up = (np.asarray(T.as_f64_list(v, 3), np.float64) for v in (eye, target, up))
+        self.width, self.height = int(width), int(height)
+        check_sizes(self.width, self.height)
+        self.fov = float(fov)
+        self.ortho_height = None if ortho_height is None else float(ortho_height)
+        self.near = None if near is None else float(near)
+        self.far = None if far is None else float(far)
+        if not all(np.isfinite(v).all() for v in (self.eye, self.target, self.up)):
+            raise ValueError("camera: eye, target and up must be finite")
+        if self.ortho_height is None:
+            if not (0.0 < self.fov < 180.0):
+                raise ValueError(f"camera: fov must be in (0, 180) degrees, got {self.fov}")
+        elif not (math.isfinite(self.ortho_height) and self.ortho_height > 0):
+            raise ValueError(f"camera: ortho_height must be positive, got {self.ortho_height}")
+        for name, v in (("near", self.near), ("far", self.far)):
+            if v is not None and not math.isfinite(v):
+                raise ValueError(f"camera: {name} must be finite, got {v}")
+        if self.near is not None and self.far is not None and not self.far > self.near:
+            raise ValueError(f"camera: far ({self.far}) must be > near ({self.near})")
+        view = self.target - self.eye
+        if not float(np.abs(view).max()) > 0:
+            raise ValueError("camera: eye and target coincide")
+        side = np.cross(_unit(view), self.up)
+        if not float(np.sqrt((side * side).sum())) > 1e-12 * float(np.sqrt((self.up * self.up).sum())) > 0:
+            raise ValueError("camera: up is zero or parallel to the view direction")
+        b = self.basis()
+        if not all(np.isfinite(b[k]).all() for k in ("f", "r", "u")) or not (math.isfinite(b["half_w"]) and b["half_w"] > 0
+                                                                              and b["half_h"] > 0):
+            raise ValueError("camera: degenerate frame")
+
+    @property
+    def ortho(self):
+        return self.ortho_height is not None
+
+    def basis(self):
+        """dict(eye, f, r, u, half_w, half_h, ortho) in float64: f = normalize(target - eye), r = normalize(cross(f, up)),
+        u = cross(r, f); half_h = tan(fov / 2) or ortho_height / 2, half_w = half_h * width / height.  These travel to the
+        kernels by value."""
+        f = _unit(self.target - self.eye)
+        r = _unit(np.cross(f, self.up))
+        u = np.cross(r, f)
+        half_h = float(np.tan(np.deg2rad(np.float64(self.fov)) / 2.0)) if self.ortho_height is None else self.ortho_height / 2.0
+        return dict(eye=self.eye.copy(), f=f, r=r, u=u, half_w=half_h * self.width / self.height, half_h=half_h,
+                    ortho=self.ortho)
+
+    def packed(self):
+        b = self.basis()
+        return [float(v) for k in ("eye", "f", "r", "u") for v in b[k]] + [b["half_w"], b["half_h"]]
+
+    def range(self, shapes, step):
+        """(near, far): the camera's own where given; otherwise from the corners of the shapes' posed boxes -- along the
+        view axis for the near end (a ray's parameter is at least that), the distance from the eye for the far end
+        (orthographic: the view axis for both) -- one step wider"""
+        if self.near is not None and self.far is not None:
+            return self.near, self.far
+        b = self.basis()
+        lo, hi = math.inf, -math.inf
+        for s in shapes:
+            n = np.asarray(s.volume.phi.shape, np.float64) - 1.0
+            org, h = np.asarray(T.as_f64_list(s.volume.origin, 3)), float(s.volume.spacing)
+            for c in np.ndindex(2, 2, 2):
+                p = s.R @ (org + np.asarray(c, np.float64) * n * h) + s.T - b["eye"]
+                along = float(p @ b["f"])
+                lo = min(lo, along)
+                hi = max(hi, along if self.ortho else float(np.sqrt(p @ p)))
+        near = self.near if self.near is not None else (lo - step if self.ortho else max(lo - step, 0.0))
+        far = self.far if self.far is not None else max(hi + step, near + step)
+        return near, far
+
+
+class RenderResult(NamedTuple):
+    """depth (H, W) float64, the distance along the ray, +inf at a miss; normal (H, W, 3) float32, 0 at a miss; shape_id
+    (H, W) int32, -1 at a miss; steps (H, W) int32, the index of the hit sample, -1 at a miss; near / far / step /
+    num_steps: the march as it was run; num_shapes: of the scene."""
+    depth: torch.Tensor
+    normal: torch.Tensor
+    shape_id: torch.Tensor
+    steps: torch.Tensor
+    near: float
+    far: float
+    step: float
+    num_steps: int
+    num_shapes: int
+
+
+def _shapes(shapes, device=True):
+    """a shape or a list of shapes -> a list of `mfs.seed.Shape`, after the checks that need no device, then (device=True)
+    the device checks"""
+    out = _seed._shape_list(shapes)
+    if not (1 <= len(out) <= MAX_SHAPES):
+        raise ValueError(f"{len(out)} shapes: a scene has 1 .. {MAX_SHAPES}")
+    for k, s in enumerate(out):
+        name = f"shape[{k}]"
+        phi = s.volume.phi
+        if not isinstance(phi, torch.Tensor):
+            raise TypeError(f"{name}.phi: expected a torch tensor on the GPU, got {type(phi).__name__}")
+        if phi.dim() != 3 or min(phi.shape) < 2 or phi.numel() > 2 ** 31 - 1:
+            raise ValueError(f"{name}.phi: expected a volume (n0, n1, n2), every extent >= 2, fewer than 2^31 nodes, got "
+                             f"{tuple(phi.shape)}")
+        if phi.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"{name}.phi: dtype {phi.dtype} unsupported (float32 / float64)")
+        if not phi.is_contiguous():
+            raise ValueError(f"{name}.phi: tensor must be C-contiguous")
+        h = float(s.volume.spacing)
+        if not (math.isfinite(h) and h > 0):
+            raise ValueError(f"{name}.spacing must be positive, got {h}")
+        if not (all(math.isfinite(v) for v in T.as_f64_list(s.volume.origin, 3)) and np.isfinite(s.T).all()
+                and np.isfinite(s.R).all()):
+            raise ValueError(f"{name}: origin and pose must be finite")
+    for k, s in enumerate(out if device else ()):
+        phi = s.volume.phi
+        if not phi.is_cuda:
+            raise TypeError(f"shape {k}: volume is on {phi.device}; rendering runs on the GPU only (no CPU fallback)")
+        if phi.device != out[0].volume.phi.device:
+            raise ValueError(f"shape {k}: volume is on {phi.device}, shape 0 on {out[0].volume.phi.device}; all volumes must "
+                             "be on one device")
+    return out
+
+
+def plan(shapes, camera, step=None):
+    """(near, far, step, num_steps) of a march of `shapes` (as `_shapes` returns them) seen by `camera`, after every
+    refusal that needs no device: step defaults to half the smallest spacing, near / far to the camera's or the shapes'
+    boxes, num_steps = ceil((far - near) / step) must be in 1 .. 65536"""
+    if not isinstance(camera, Camera):
+        raise TypeError(f"camera: expected an mfs.render.Camera, got {type(camera).__name__}")
+    step = 0.5 * min(float(s.volume.spacing) for s in shapes) if step is None else float(step)
+    if not (math.isfinite(step) and step > 0):
+        raise ValueError(f"step must be positive, got {step}")
+    near, far = camera.range(shapes, step)
+    if not (math.isfinite(near) and math.isfinite(far) and far > near):
+        raise ValueError(f"camera: marched interval [{near}, {far}] is empty or not finite")
+    K = math.ceil((far - near) / step)
+    check_sizes(camera.width, camera.height, K)
+    return near, far, step, K
+
+
+class Scene:
+    """1 to 16 shapes (anything `mfs.seed.as_shape` accepts; float32 / float64 volumes on one GPU) and, per shape, the
+    grid of brick minima the marcher skips by.  The grids are built here; call `refresh()` after a volume's contents
+    changed (a volume replaced by another tensor needs a new Scene)."""
+
+    def __init__(self, shapes):
+        self.shapes = _shapes(shapes)
+        self.device = self.shapes[0].volume.phi.device
+        self.bricks = []
+        self.refresh()
+
+    def refresh(self):
+        """rebuild every shape's brick minima from its volume as it is now"""
+        lib = _lib.load()
+        self.bricks = []
+        with torch.cuda.device(self.device):
+            for s in self.shapes:
+                phi = s.volume.phi
+                e = _lib.i64x(phi.shape)
+                grid = torch.empty(tuple((int(n) - 2) // BRICK + 1 for n in phi.shape), dtype=torch.float64, device=self.device)
+                assert grid.numel() == int(lib.mfs_render_brick_count3d(e))
+                _lib.check(lib.mfs_render_bricks3d(T.ptr(phi), T.code(phi), e, T.ptr(grid), T.stream()), "mfs_render_bricks3d")
+                self.bricks.append(grid)
+        return self
+
+    def render(self, camera, step=None, skip=True, stats=None):
+        """March every pixel of `camera` (module docstring).  step: the sample distance along the ray, default half the
+        smallest spacing.  skip=False visits every sample of every shape: the same bits, more work.  stats: an optional
+        dict that receives `pixels`, `hits`, `samples` (shape samples evaluated) and `num_steps` (one host sync)."""
+        near, far, step, K = plan(self.shapes, camera, step)
+        W, H = camera.width, camera.height
+        lib = _lib.load()
+        m, dev = len(self.shapes), self.device
+        vols, grids, dts, ext, orgs, sps, poses = (ctypes.c_void_p * m)(), (ctypes.c_void_p * m)(), [], [], [], [], []
+        for i, s in enumerate(self.shapes):
+            phi = s.volume.phi
+            vols[i], grids[i] = phi.data_ptr(), self.bricks[i].data_ptr()
+            dts.append(T.code(phi))
+            ext += [int(v) for v in phi.shape]
+            orgs += T.as_f64_list(s.volume.origin, 3)
+            sps.append(float(s.volume.spacing))
+            poses += [float(v) for v in s.R.reshape(-1)] + [float(v) for v in s.T]
+        with torch.cuda.device(dev):
+            depth = torch.empty((H, W), dtype=torch.float64, device=dev)
+            normal = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+            ident = torch.empty((H, W), dtype=torch.int32, device=dev)
+            steps = torch.empty((H, W), dtype=torch.int32, device=dev)
+            evals = torch.empty((H, W), dtype=torch.int32, device=dev) if stats is not None else None
+            _lib.check(lib.mfs_render_march3d(_lib.f64x(camera.packed()), int(camera.ortho), W, H, near, step, K, m, vols,
+                                              (ctypes.c_int * m)(*dts), _lib.i64x(ext), _lib.f64x(orgs), _lib.f64x(sps),
+                                              _lib.f64x(poses), grids, int(bool(skip)), T.ptr(depth), T.ptr(normal),
+                                              T.ptr(ident), T.ptr(steps), None if evals is None else T.ptr(evals), T.stream()),
+                       "mfs_render_march3d")
+            if stats is not None:
+                stats.update(pixels=W * H, hits=int((steps >= 0).sum().item()),
+                             samples=int(evals.sum(dtype=torch.int64).item()), num_steps=K)
+        return RenderResult(depth, normal, ident, steps, near, far, step, K, m)
+
+
+def _palette(colors, count):
+    if colors is None or len(colors) < count or len(colors) > MAX_SHAPES:
+        raise ValueError(f"colors: expected one (r, g, b) in 0 .. 255 per shape ({count}), at most {MAX_SHAPES}")
+    out = []
+    for c in colors:
+        c = T.as_f64_list(c, 3)
+        if not all(0.0 <= v <= 255.0 for v in c):
+            raise ValueError(f"colors: components must be in 0 .. 255, got {tuple(c)}")
+        out += [v / 255.0 for v in c]
+    return out
+
+
+def shade(result, camera, colors, background=(255, 255, 255), light=None):
+    """(H, W, 3) uint8 on the result's device: albedo_id * (0.25 + 0.75 * max(0, n . l)), albedo = colour / 255, rounded
+    floor(255 c + 0.5); l = -d, a headlight, or `light`, a vector towards the light; `background` at misses."""
+    if not isinstance(result, RenderResult):
+        raise TypeError(f"result: expected a RenderResult, got {type(result).__name__}")
+    if not isinstance(camera, Camera):
+        raise TypeError(f"camera: expected an mfs.render.Camera, got {type(camera).__name__}")
+    H, W = (int(v) for v in result.steps.shape)
+    if (camera.width, camera.height) != (W, H):
+        raise ValueError(f"camera is {camera.width} x {camera.height}, the result {W} x {H}")
+    albedo = _palette(colors, result.num_shapes)
+    bg = [int(v) for v in background]
+    if len(bg) != 3 or not all(0 <= v <= 255 for v in bg):
+        raise ValueError(f"background: expected (r, g, b) in 0 .. 255, got {tuple(background)}")
+    if light is not None:
+        light = np.asarray(T.as_f64_list(light, 3), np.float64)
+        if not (np.isfinite(light).all() and float(np.abs(light).max()) > 0):
+            raise ValueError("light: expected a finite, non-zero vector towards the light")
+        light = _unit(light)
+    if not result.normal.is_cuda:
+        raise TypeError(f"result is on {result.normal.device}; shading runs on the GPU only (no CPU fallback)")
+    lib = _lib.load()
+    dev = result.normal.device
+    with torch.cuda.device(dev):
+        rgb = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+        _lib.check(lib.mfs_render_shade3d(_lib.f64x(camera.packed()), int(camera.ortho), W, H, T.ptr(result.normal),
+                                          T.ptr(result.shape_id), len(albedo) // 3, _lib.f64x(albedo), (ctypes.c_int * 3)(*bg),
+                                          None if light is None else _lib.f64x(light), T.ptr(rgb), T.stream()),
+                   "mfs_render_shade3d")
+    return rgb
+
+
+def image(shapes, camera, colors, background=(255, 255, 255), light=None, step=None, skip=True):
+    """`Scene(shapes).render(camera, step, skip)` shaded: (H, W, 3) uint8"""
+    listed = _shapes(shapes, device=False)                                # everything a host can refuse, first
+    plan(listed, camera, step)
+    _palette(colors, len(listed))
+    return shade(Scene(listed).render(camera, step, skip), camera, colors, background, light)
+
+
+def _chunk(tag, data):
+    return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+
+
+def save_png(path, rgb):
+    """write (H, W, 3) uint8 (a tensor on any device, or an array) as an 8-bit RGB PNG; standard library only"""
+    a = rgb.detach().cpu().numpy() if isinstance(rgb, torch.Tensor) else np.asarray(rgb)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"rgb: expected (H, W, 3) uint8, got {a.shape} {a.dtype}")
+    H, W = a.shape[:2]
+    rows = np.concatenate([np.zeros((H, 1), np.uint8), np.ascontiguousarray(a).reshape(H, 3 * W)], axis=1)   # filter 0
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0))
+                + _chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + _chunk(b"IEND", b""))
+
+
+# ------------------------------------------------------------------------------------------- NotebookSimulation ----
+class _Volume(NamedTuple):
+    phi: torch.Tensor
+    origin: tuple
+    spacing: float
+
+
+LIQUID_COLOR, SOLID_COLOR = (40, 120, 230), (190, 185, 175)
+
+
+def simulation_shapes(sim, what=("liquid", "solid")):
+    """the shapes of `NotebookSimulation.render`: "liquid" = skin_field(clip=True), "solid" = solid_levelset.phi as a bare
+    volume (origin bound_min, spacing GDX / 2: the analytic and the mesh bodies united), in the order of `what`"""
+    what = (what,) if isinstance(what, str) else tuple(what)
+    if not what or any(w not in ("liquid", "solid") for w in what) or len(set(what)) != len(what):
+        raise ValueError(f'what: expected "liquid", "solid" or both, got {what!r}')
+    out = []
+    for w in what:
+        if w == "liquid":
+            out.append(sim.skin_field(clip=True))
+        else:
+            sl = sim.solid_levelset
+            out.append(_Volume(sl.phi, tuple(float(v) for v in np.asarray(sl.bound_min, np.float64)), 0.5 * sim.GDX))
+    return what, out
+
+
+def simulation_result(sim, camera, what=("liquid", "solid"), step=None):
+    return Scene(simulation_shapes(sim, what)[1]).render(camera, step)
+
+
+def simulation_image(sim, camera, what=("liquid", "solid"), colors=None, step=None):
+    names, shapes = simulation_shapes(sim, what)
+    if colors is None:
+        colors = [LIQUID_COLOR if w == "liquid" else SOLID_COLOR for w in names]
+    return image(shapes, camera, colors, step=step)

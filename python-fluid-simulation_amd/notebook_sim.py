@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 import notebook_kernels as K
+from mfs import render as _render
 from mfs import skin as _skin
 from mfs import surface as _surface
 from mfs.motion import BodyKinematics
@@ -165,6 +166,17 @@ class NotebookSimulation:
         field the pressure solve sees (spheres of 0.88 GDX at cell centres); this shows the liquid."""
         return _skin.extract(self.skin_field(clip, radius, influence), normals=normals)
 
+    def render_result(self, camera, what=("liquid", "solid"), step=None):
+        """The scene ray-marched on the GPU, unshaded (`mfs.render.RenderResult`: depth, normal, shape id, step index per
+        pixel of `camera`, an `mfs.render.Camera`).  what: "liquid" = `skin_field(clip=True)`, "solid" =
+        `solid_levelset.phi` (the analytic and the mesh bodies united); shape ids count in the order of `what`."""
+        return _render.simulation_result(self, camera, what, step)
+
+    def render(self, camera, what=("liquid", "solid"), colors=None, step=None):
+        """`render_result` shaded: an (H, W, 3) uint8 image on the GPU, white where a ray meets nothing;
+        `mfs.render.save_png` writes it.  colors: one (r, g, b) in 0 .. 255 per entry of `what`."""
+        return _render.simulation_image(self, camera, what, colors, step)
+
     def step(self, duration_left=float("inf"), timings=None):
         """One pass of the loop body (ipynb:4571-4667, solver == 'apic').  Returns the dt it took."""
         p, g, sl, fl, fv = self.particle, self.grid, self.solid_levelset, self.fluid_levelset, self.fluid_volume
@@ -286,6 +298,13 @@ class SlabNotebookSimulation(NotebookSimulation):
 
     def skin_field(self, clip=True, radius=None, influence=None):
         raise NotImplementedError("skin() is single-GPU: gather the particles to one rank and call mfs.skin.field")
+
+    def render_result(self, camera, what=("liquid", "solid"), step=None):
+        raise NotImplementedError("render() is single-GPU: gather the particles and the level set to one rank and call "
+                                  "mfs.render.image")
+
+    def render(self, camera, what=("liquid", "solid"), colors=None, step=None):
+        return self.render_result(camera, what, step)
 
     def close(self):
         self.PressureSolver.close()
