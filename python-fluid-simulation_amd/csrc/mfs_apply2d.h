@@ -11,14 +11,6 @@
 
 namespace mfs {
 
-__device__ __forceinline__ double edge_in_fraction2(double l, double r) {  // SolidFractionCommon.py:4-16
-  const bool li = l < 0, ri = r < 0;
-  if (li && ri) return 1.0;
-  if (!li && !ri) return 0.0;
-  const double diff = -fabs(l - r);
-  return li ? l / diff : r / diff;
-}
-
 struct Grid2 {
   int Nx, Ny;
   __device__ int64_t c(int x, int y) const { return (int64_t)x * Ny + y; }

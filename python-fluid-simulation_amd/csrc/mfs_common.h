@@ -46,6 +46,18 @@ __device__ __forceinline__ double ldx(const void* p, int dt, int64_t i) {
 __device__ __forceinline__ void stx(void* p, int dt, int64_t i, double v) {
   if (dt == MFS_F32) ((float*)p)[i] = (float)v; else ((double*)p)[i] = v;
 }
+__device__ __forceinline__ void atomic_addx(void* p, int dt, int64_t i, double v) {
+  if (dt == MFS_F32) atomicAdd((float*)p + i, (float)v); else atomicAdd((double*)p + i, v);
+}
+
+// fraction of the edge (l, r) of a level set that lies inside (< 0): solver/SolidFractionCommon.py:4-16
+__device__ __forceinline__ double edge_in_fraction(double l, double r) {
+  const bool li = l < 0, ri = r < 0;
+  if (li && ri) return 1.0;
+  if (!li && !ri) return 0.0;
+  const double diff = -fabs(l - r);
+  return li ? l / diff : r / diff;
+}
 
 // ------------------------------------------------------------ reductions ----
 constexpr int kWave = 64;

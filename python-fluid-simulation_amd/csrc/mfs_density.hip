@@ -28,19 +28,6 @@ struct DGrid {
 };
 struct D3 { double v[3]; };
 
-// solver/SolidFractionCommon.py:4-16
-__device__ __forceinline__ double d_edge_in_fraction(double l, double r) {
-  const bool li = l < 0, ri = r < 0;
-  if (li && ri) return 1.0;
-  if (!li && !ri) return 0.0;
-  const double diff = -fabs(l - r);
-  return li ? l / diff : r / diff;
-}
-
-__device__ __forceinline__ void atomic_addx(void* p, int dt, int64_t i, double v) {
-  if (dt == MFS_F32) atomicAdd((float*)p + i, (float)v); else atomicAdd((double*)p + i, v);
-}
-
 // trilinear stencil of a particle on a grid whose samples sit at (index + bias) * cell_size + bound_min:
 // base index gi and the |gx - x| / cell_size weights, exactly as :17-22 / :235-239
 __device__ __forceinline__ void particle_cell(const void* px, int pdt, int64_t P, D3 bmin, D3 cs, D3 bias, long long gi[3],
@@ -215,9 +202,9 @@ k_density_displacement(DGrid g, double dt, D3 cs, void* dx, void* dy, void* dz, 
   if (x == 0 || y == 0 || z == 0) return;
   const int64_t sx = (int64_t)g.Ny * g.Nz, sy = g.Nz;
   const double pc = ldx(lphi, ldt, i), p = ldx(pv, pdt, i);
-  const double phix = fmin(1.0, fmax(0.01, d_edge_in_fraction(pc, ldx(lphi, ldt, i - sx))));
-  const double phiy = fmin(1.0, fmax(0.01, d_edge_in_fraction(pc, ldx(lphi, ldt, i - sy))));
-  const double phiz = fmin(1.0, fmax(0.01, d_edge_in_fraction(pc, ldx(lphi, ldt, i - 1))));
+  const double phix = fmin(1.0, fmax(0.01, edge_in_fraction(pc, ldx(lphi, ldt, i - sx))));
+  const double phiy = fmin(1.0, fmax(0.01, edge_in_fraction(pc, ldx(lphi, ldt, i - sy))));
+  const double phiz = fmin(1.0, fmax(0.01, edge_in_fraction(pc, ldx(lphi, ldt, i - 1))));
   stx(dx, ddt, g.fx(x, y, z), (p - ldx(pv, pdt, i - sx)) * dt * cs.v[0] / phix);
   stx(dy, ddt, g.fy(x, y, z), (p - ldx(pv, pdt, i - sy)) * dt * cs.v[1] / phiy);
   stx(dz, ddt, g.fz(x, y, z), (p - ldx(pv, pdt, i - 1)) * dt * cs.v[2] / phiz);

@@ -22,10 +22,6 @@ namespace mfs {
 
 struct D2 { double v[2]; };
 
-__device__ __forceinline__ void atomic_addx2(void* p, int dt, int64_t i, double v) {
-  if (dt == MFS_F32) atomicAdd((float*)p + i, (float)v); else atomicAdd((double*)p + i, v);
-}
-
 // bilinear stencil of a particle on a grid whose samples sit at (index + bias) * cell_size + bound_min:
 // base index gi and the |gx - x| / cell_size weights, exactly as :19-23 / :182-186
 __device__ __forceinline__ void particle_cell2(const void* px, int pdt, int64_t P, D2 bmin, D2 cs, D2 bias, long long gi[2],
@@ -55,7 +51,7 @@ k_density_splat2d(Grid2 g, D2 bmin, D2 cs, const void* px, int pxdt, const void*
       const int cx = (int)max(0LL, min((long long)g.Nx - 1, gi[0] + ix));
       const int cy = (int)max(0LL, min((long long)g.Ny - 1, gi[1] + iy));
       const double weight = corner_weight2(ix, w[0]) * corner_weight2(iy, w[1]);
-      atomic_addx2(gm, gdt, g.c(cx, cy), weight * m);
+      atomic_addx(gm, gdt, g.c(cx, cy), weight * m);
     }
 }
 
@@ -110,8 +106,8 @@ k_density_displacement2d(Grid2 g, double dt, D2 cs, void* dx, void* dy, int ddt,
   const int y = (int)(i % g.Ny), x = (int)(i / g.Ny);
   if (x == 0 || y == 0) return;
   const double pc = ldx(lphi, ldt, i), p = ldx(pv, pdt, i);
-  const double phix = fmin(1.0, fmax(0.01, edge_in_fraction2(pc, ldx(lphi, ldt, i - g.Ny))));
-  const double phiy = fmin(1.0, fmax(0.01, edge_in_fraction2(pc, ldx(lphi, ldt, i - 1))));
+  const double phix = fmin(1.0, fmax(0.01, edge_in_fraction(pc, ldx(lphi, ldt, i - g.Ny))));
+  const double phiy = fmin(1.0, fmax(0.01, edge_in_fraction(pc, ldx(lphi, ldt, i - 1))));
   stx(dx, ddt, g.fx(x, y), (p - ldx(pv, pdt, i - g.Ny)) * dt * cs.v[0] / phix);
   stx(dy, ddt, g.fy(x, y), (p - ldx(pv, pdt, i - 1)) * dt * cs.v[1] / phiy);
 }

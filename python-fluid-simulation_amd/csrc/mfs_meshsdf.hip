@@ -7,13 +7,13 @@
 #include <math.h>
 
 #include "mfs_common.h"
+#include "mfs_volume.h"
 
 namespace mfs {
 
 constexpr int kMeshBlock = 256;        // threads per workgroup = triangles per LDS batch
 constexpr int kB0 = 4, kB1 = 8, kB2 = 8;   // brick of nodes owned by one workgroup of k_mesh_distance (i2 fastest)
 constexpr int kC1 = 16, kC2 = 16;      // tile of columns owned by one workgroup of k_mesh_sign (i2 fastest)
-constexpr int kMaxMeshBodies = 16;
 
 struct Lattice {
   int n[3];
@@ -168,7 +168,8 @@ k_mesh_distance(Lattice L, const float* __restrict__ tri, int F, int cull, float
 }
 
 // From here on every expression rounds as written: the sign pass needs the two triangles of an edge to evaluate the SAME
-// bits, and the union / projection kernels are restated in numpy operation by operation (tests/meshsdf_numpy.py).  The
+// bits, and the union / projection kernels are restated in numpy operation by operation (tests/meshsdf_numpy.py; their
+// sampler is mfs_volume.h's).  The
 // distance kernel above keeps the compiler's default contraction: cull on / off run the same code, so they still agree
 // bit for bit.
 #pragma clang fp contract(off)
@@ -267,13 +268,8 @@ k_mesh_sign(Lattice L, const float* __restrict__ tri, int F, float* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------- posed mesh bodies ----
-struct MeshVolumes {                       // by value in the launch: at most kMaxMeshBodies bodies
-  const float* vol[kMaxMeshBodies];
-  int n[kMaxMeshBodies][3];
-  double org[kMaxMeshBodies][3];
-  double h[kMaxMeshBodies];
-};
-
+// The bodies' volumes travel as mfs_volume.h's Volumes, float32 all (dt = MFS_F32); their poses are read from the device
+// body table.
 struct MeshPose {
   double T[3];
   double R[3][3];
@@ -290,87 +286,27 @@ __device__ __forceinline__ MeshPose pose_load(const double* __restrict__ rb, int
   return r;
 }
 
-// x_b = R^T (x - T)
-__device__ __forceinline__ void pose_to_body(const MeshPose& r, const double x[3], double out[3]) {
-  const double d[3] = {x[0] - r.T[0], x[1] - r.T[1], x[2] - r.T[2]};
-  for (int i = 0; i < 3; ++i) out[i] = (r.R[0][i] * d[0] + r.R[1][i] * d[1]) + r.R[2][i] * d[2];
-}
-
-// Trilinear sample of body i's volume at the body-frame point xb; outside the volume: the sample at the clamped point plus
-// the distance to the volume's box.  grad (may be null): the gradient of that function in the body frame -- along an axis
-// where the point was clamped the sample does not vary and only the distance term contributes.
-__device__ __forceinline__ double volume_sample(const MeshVolumes& V, int i, const double xb[3], double* grad) {
-  int c[3];
-  double f[3], e[3];
-  bool in[3];
-  for (int k = 0; k < 3; ++k) {
-    const double t = (xb[k] - V.org[i][k]) / V.h[i];
-    const double hi = (double)(V.n[i][k] - 1);
-    const double tc = fmin(fmax(t, 0.0), hi);
-    int ci = (int)floor(tc);
-    if (ci > V.n[i][k] - 2) ci = V.n[i][k] - 2;
-    c[k] = ci;
-    f[k] = tc - (double)ci;
-    e[k] = (t - tc) * V.h[i];
-    in[k] = t == tc;
-  }
-  const int64_t s0 = (int64_t)V.n[i][1] * V.n[i][2], s1 = V.n[i][2];
-  const float* p = V.vol[i] + (c[0] * s0 + c[1] * s1 + c[2]);
-  const double v000 = p[0], v001 = p[1], v010 = p[s1], v011 = p[s1 + 1];
-  const double v100 = p[s0], v101 = p[s0 + 1], v110 = p[s0 + s1], v111 = p[s0 + s1 + 1];
-  const double g0 = 1.0 - f[0], g1 = 1.0 - f[1], g2 = 1.0 - f[2];
-  const double c00 = v000 * g2 + v001 * f[2], c01 = v010 * g2 + v011 * f[2];
-  const double c10 = v100 * g2 + v101 * f[2], c11 = v110 * g2 + v111 * f[2];
-  const double c0 = c00 * g1 + c01 * f[1], c1 = c10 * g1 + c11 * f[1];
-  const double dist = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-  if (grad) {
-    const double a00 = v000 * g1 + v010 * f[1], a01 = v001 * g1 + v011 * f[1];   // along axis 1, for d/dx2
-    const double a10 = v100 * g1 + v110 * f[1], a11 = v101 * g1 + v111 * f[1];
-    grad[0] = in[0] ? (c1 - c0) / V.h[i] : 0.0;
-    grad[1] = in[1] ? ((c01 - c00) * g0 + (c11 - c10) * f[0]) / V.h[i] : 0.0;
-    grad[2] = in[2] ? ((a01 - a00) * g0 + (a11 - a10) * f[0]) / V.h[i] : 0.0;
-    if (dist > 0.0)
-      for (int k = 0; k < 3; ++k) grad[k] += e[k] / dist;
-  }
-  return (c0 * g0 + c1 * f[0]) + dist;
-}
-
-struct UnionGrid {
-  int64_t n1, n2, total;
-  double bmin[3];
-  float bias[3];
-  double cs[3];
-};
-
 // sd / vel hold a solid level set already (k_sdf_evaluate_grid's, or any); every mesh body in turn: d < sd -> sd = d and
 // vel = (d <= 0 ? v + w x (x - T) : 0), k_sdf_evaluate_grid's rule.  The running minimum is kept in float64 across the
 // bodies and stored once; nodes no body wins are not written.
 __global__ void __launch_bounds__(256)
-k_mesh_union_grid(const double* __restrict__ rb, const double* __restrict__ rb_w, int m, MeshVolumes V, UnionGrid a,
+k_mesh_union_grid(const double* __restrict__ rb, const double* __restrict__ rb_w, int m, Volumes V, GridArgs3 a,
                   void* sd, int sdt, void* vel, int vdt) {
   const int64_t base = (int64_t)blockIdx.x * 256;
   const int64_t p = base + threadIdx.x;
   if (p >= a.total) return;
-  const int64_t row = base / a.n2;                     // as k_sdf_evaluate_grid: 64-bit divisions per block only
-  uint32_t i2 = (uint32_t)(base - row * a.n2) + threadIdx.x;
-  const uint32_t q2 = i2 / (uint32_t)a.n2;
-  i2 -= q2 * (uint32_t)a.n2;
-  int64_t i0 = row / a.n1;
-  uint32_t i1 = (uint32_t)(row - i0 * a.n1) + q2;
-  const uint32_t q1 = i1 / (uint32_t)a.n1;
-  i1 -= q1 * (uint32_t)a.n1;
-  i0 += q1;
-  const double pos[3] = {a.bmin[0] + (double)((float)i0 + a.bias[0]) * a.cs[0],
-                         a.bmin[1] + (double)((float)i1 + a.bias[1]) * a.cs[1],
-                         a.bmin[2] + (double)((float)i2 + a.bias[2]) * a.cs[2]};
+  const LatticeIndex at = lattice_split(base, threadIdx.x, a.n1, a.n2);
+  const double pos[3] = {a.bmin[0] + (double)((float)at.i0 + a.bias[0]) * a.cs[0],
+                         a.bmin[1] + (double)((float)at.i1 + a.bias[1]) * a.cs[1],
+                         a.bmin[2] + (double)((float)at.i2 + a.bias[2]) * a.cs[2]};
   double cur = ldx(sd, sdt, p);
   double v[3] = {0.0, 0.0, 0.0};
   bool won = false;
   for (int i = 0; i < m; ++i) {
     const MeshPose r = pose_load(rb, i);
     double xb[3];
-    pose_to_body(r, pos, xb);
-    const double d = volume_sample(V, i, xb, nullptr);
+    pose_to_body(r.R, r.T, pos, xb);
+    const double d = volume_sample<true>(V, i, xb);
     if (d < cur) {
       cur = d;
       won = true;
@@ -397,7 +333,7 @@ k_mesh_union_grid(const double* __restrict__ rb, const double* __restrict__ rb_w
 // k_sdf_project): sampled d < 0 -> x -= d * R n, n the normalised gradient of the sampled volume.  A vanishing gradient
 // falls back to central differences of samples one spacing apart; still zero: the particle stays.  d >= 0: no store.
 __global__ void __launch_bounds__(256)
-k_mesh_project(const double* __restrict__ rb, int m, MeshVolumes V, void* position, int pdt, int64_t P) {
+k_mesh_project(const double* __restrict__ rb, int m, Volumes V, void* position, int pdt, int64_t P) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= P) return;
   double pos[3] = {ldx(position, pdt, 3 * p), ldx(position, pdt, 3 * p + 1), ldx(position, pdt, 3 * p + 2)};
@@ -405,8 +341,8 @@ k_mesh_project(const double* __restrict__ rb, int m, MeshVolumes V, void* positi
   for (int i = 0; i < m; ++i) {
     const MeshPose r = pose_load(rb, i);
     double xb[3], g[3];
-    pose_to_body(r, pos, xb);
-    const double d = volume_sample(V, i, xb, g);
+    pose_to_body(r.R, r.T, pos, xb);
+    const double d = volume_sample<true>(V, i, xb, nullptr, nullptr, g);
     if (!(d < 0)) continue;
     double nn = sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
     if (!(nn > 0)) {
@@ -414,7 +350,7 @@ k_mesh_project(const double* __restrict__ rb, int m, MeshVolumes V, void* positi
         double xp[3] = {xb[0], xb[1], xb[2]}, xm[3] = {xb[0], xb[1], xb[2]};
         xp[k] += V.h[i];
         xm[k] -= V.h[i];
-        g[k] = volume_sample(V, i, xp, nullptr) - volume_sample(V, i, xm, nullptr);
+        g[k] = volume_sample<true>(V, i, xp) - volume_sample<true>(V, i, xm);
       }
       nn = sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
       if (!(nn > 0)) continue;
@@ -432,12 +368,8 @@ k_mesh_project(const double* __restrict__ rb, int m, MeshVolumes V, void* positi
 }
 
 static int fill_lattice(Lattice* L, const int64_t shape[3], const double origin[3], double spacing) {
-  MFS_REQUIRE(shape && origin, "null lattice description");
-  MFS_REQUIRE(shape[0] >= 2 && shape[1] >= 2 && shape[2] >= 2, "lattice extents must be >= 2");
-  MFS_REQUIRE(shape[0] < ((int64_t)1 << 31) / shape[1] / shape[2], "lattice node count must stay below 2^31");
-  MFS_REQUIRE(spacing > 0 && isfinite(spacing), "spacing must be positive");
+  if (int st = check_lattice(shape, origin, spacing)) return st;
   for (int k = 0; k < 3; ++k) {
-    MFS_REQUIRE(isfinite(origin[k]), "origin must be finite");
     L->n[k] = (int)shape[k];
     L->org[k] = origin[k];
   }
@@ -445,24 +377,12 @@ static int fill_lattice(Lattice* L, const int64_t shape[3], const double origin[
   return MFS_OK;
 }
 
-static int fill_volumes(MeshVolumes* V, int64_t m, const void* const* volumes_host, const int64_t* extents_host,
-                        const double* origins_host, const double* spacings_host) {
-  MFS_REQUIRE(m >= 0 && m <= kMaxMeshBodies, "at most 16 mesh bodies per call");
+// the bodies' volumes of a C entry point: float32, no host poses
+static int fill_mesh_volumes(Volumes* V, int64_t m, const void* const* volumes_host, const int64_t* extents_host,
+                             const double* origins_host, const double* spacings_host) {
+  MFS_REQUIRE(m >= 0 && m <= kMaxVolumes, "at most 16 mesh bodies per call");
   MFS_REQUIRE(m == 0 || (volumes_host && extents_host && origins_host && spacings_host), "null mesh volume description");
-  memset(V, 0, sizeof(*V));
-  for (int64_t i = 0; i < m; ++i) {
-    MFS_REQUIRE(volumes_host[i], "null mesh volume");
-    MFS_REQUIRE(spacings_host[i] > 0 && isfinite(spacings_host[i]), "mesh volume spacing must be positive");
-    const int64_t* e = extents_host + 3 * i;
-    MFS_REQUIRE(e[0] >= 2 && e[1] >= 2 && e[2] >= 2 && e[0] < ((int64_t)1 << 31) / e[1] / e[2], "mesh volume extents");
-    V->vol[i] = (const float*)volumes_host[i];
-    V->h[i] = spacings_host[i];
-    for (int k = 0; k < 3; ++k) {
-      V->n[i][k] = (int)e[k];
-      V->org[i][k] = origins_host[3 * i + k];
-    }
-  }
-  return MFS_OK;
+  return fill_volumes(V, nullptr, (int)m, volumes_host, nullptr, extents_host, origins_host, spacings_host, nullptr);
 }
 
 }  // namespace mfs
@@ -508,26 +428,14 @@ int mfs_mesh_union_grid3d(const void* mesh_rb, const void* rb_w, int64_t num_bod
                           const int64_t* extents_host, const double* origins_host, const double* spacings_host,
                           const int64_t res[3], const double bound_min[3], const double bias[3],
                           const double cell_size[3], void* sd, int sd_dt, void* vel, int vel_dt, mfs_stream stream) {
-  MeshVolumes V;
-  if (int st = fill_volumes(&V, num_bodies, volumes_host, extents_host, origins_host, spacings_host)) return st;
+  Volumes V;
+  if (int st = fill_mesh_volumes(&V, num_bodies, volumes_host, extents_host, origins_host, spacings_host)) return st;
   MFS_REQUIRE(num_bodies == 0 || mesh_rb, "null mesh_rb");
-  MFS_REQUIRE(res && bound_min && bias && cell_size, "null grid description");
-  const int64_t lim = (int64_t)1 << 30;
-  MFS_REQUIRE(res[0] >= 0 && res[1] >= 0 && res[2] >= 0 && res[0] <= lim && res[1] <= lim && res[2] <= lim, "grid extents");
+  GridArgs3 a;
+  if (int st = fill_grid_args(&a, res, bound_min, bias, cell_size)) return st;
   MFS_REQUIRE(dtype_ok(sd_dt) && dtype_ok(vel_dt), "dtype");
-  const int64_t rows = res[0] * res[1];
-  if (rows == 0 || res[2] == 0 || num_bodies == 0) return MFS_OK;
-  MFS_REQUIRE(rows <= (int64_t)0x7fffffff * 256 / res[2], "grid too large for one launch");
+  if (a.total == 0 || num_bodies == 0) return MFS_OK;
   MFS_REQUIRE(sd && vel, "null output arrays");
-  UnionGrid a;
-  a.n1 = res[1];
-  a.n2 = res[2];
-  a.total = rows * res[2];
-  for (int k = 0; k < 3; ++k) {
-    a.bmin[k] = (double)(float)bound_min[k];
-    a.bias[k] = (float)bias[k];
-    a.cs[k] = cell_size[k];
-  }
   hipLaunchKernelGGL(k_mesh_union_grid, dim3(cdiv(a.total, 256)), dim3(256), 0, (hipStream_t)stream,
                      (const double*)mesh_rb, (const double*)rb_w, (int)num_bodies, V, a, sd, sd_dt, vel, vel_dt);
   MFS_LAUNCH_CHECK();
@@ -537,8 +445,8 @@ int mfs_mesh_union_grid3d(const void* mesh_rb, const void* rb_w, int64_t num_bod
 int mfs_mesh_project3d(const void* mesh_rb, int64_t num_bodies, const void* const* volumes_host,
                        const int64_t* extents_host, const double* origins_host, const double* spacings_host,
                        void* position, int pos_dt, int64_t num_positions, mfs_stream stream) {
-  MeshVolumes V;
-  if (int st = fill_volumes(&V, num_bodies, volumes_host, extents_host, origins_host, spacings_host)) return st;
+  Volumes V;
+  if (int st = fill_mesh_volumes(&V, num_bodies, volumes_host, extents_host, origins_host, spacings_host)) return st;
   MFS_REQUIRE(num_bodies == 0 || mesh_rb, "null mesh_rb");
   MFS_REQUIRE(num_positions >= 0 && (num_positions == 0 || position), "null position array");
   MFS_REQUIRE(dtype_ok(pos_dt), "dtype");

@@ -43,10 +43,6 @@ __device__ __forceinline__ void nb_cell2(const void* px, int pdt, int64_t P, con
   }
 }
 
-__device__ __forceinline__ void atomic_add_q(void* p, int dt, int64_t i, double v) {
-  if (dt == MFS_F32) atomicAdd((float*)p + i, (float)v); else atomicAdd((double*)p + i, v);
-}
-
 // min of a field cell and a candidate, atomically: the two forms of mfs_particles.hip's atomic_min_t (one integer atomic on
 // the IEEE bits after a plain read, or the compare-and-swap loop; the same bits either way)
 __device__ __forceinline__ void atomic_min_q(void* p, int dt, int64_t i, double v, bool cas) {
@@ -109,8 +105,8 @@ k_p2g_scatter2d(QGrid g, QGeom geo, int axis, const void* px, int pxdt, const vo
         const double cv = ((double)disp[0] + ix * geo.cs[0]) * c0 + ((double)disp[1] + iy * geo.cs[1]) * c1;
         const double weight = wx * wy;
         const int64_t c = g.at(cx, cy);
-        atomic_add_q(gm, gdt, c, weight * m);
-        atomic_add_q(gv, gdt, c, weight * m * ((double)va + cv));
+        atomic_addx(gm, gdt, c, weight * m);
+        atomic_addx(gv, gdt, c, weight * m * ((double)va + cv));
       }
   }
 }
@@ -182,7 +178,7 @@ k_fluid_volume_splat2d(QGrid g, QGeom geo, const void* px, int pxdt, double pvol
       for (int iy = 0; iy < 2; ++iy) {
         const int cx = clampq(gi[0] + ix, g.N[0]), cy = clampq(gi[1] + iy, g.N[1]);
         const double weight = (ix + (ix ? -1.0 : 1.0) * (1 - (double)w[0])) * (iy + (iy ? -1.0 : 1.0) * (1 - (double)w[1]));
-        atomic_add_q(gvol, gdt, g.at(cx, cy), weight * pvol);
+        atomic_addx(gvol, gdt, g.at(cx, cy), weight * pvol);
       }
   }
 }

@@ -41,10 +41,6 @@ __device__ __forceinline__ void nb_cell(const void* px, int pdt, int64_t P, cons
   }
 }
 
-__device__ __forceinline__ void atomic_add_t(void* p, int dt, int64_t i, double v) {
-  if (dt == MFS_F32) atomicAdd((float*)p + i, (float)v); else atomicAdd((double*)p + i, v);
-}
-
 // min of a field cell and a candidate, atomically.  Two forms, the same bits (a minimum does not depend on the order of
 // its candidates); a plain read first in both: once the field has settled most candidates lose without touching the atomic unit.
 //  * native: ONE integer atomic -- IEEE values order like signed integers when they are >= 0 and like reversed unsigned
@@ -118,8 +114,8 @@ k_p2g_scatter(PGrid g, PGeom geo, int axis, const void* px, int pxdt, const void
                           ((double)disp[2] + iz * geo.cs[2]) * c2;
         const double weight = wx * wy * wz;
         const int64_t c = g.at(cx, cy, cz);
-        atomic_add_t(gm, gdt, c, weight * m);
-        atomic_add_t(gv, gdt, c, weight * m * ((double)va + cv));
+        atomic_addx(gm, gdt, c, weight * m);
+        atomic_addx(gv, gdt, c, weight * m * ((double)va + cv));
       }
 }
 
@@ -208,7 +204,7 @@ k_fluid_volume_splat(PGrid g, PGeom geo, const void* px, int pxdt, double pvol, 
         const int cx = clampi(gi[0] + ix, g.N[0]), cy = clampi(gi[1] + iy, g.N[1]), cz = clampi(gi[2] + iz, g.N[2]);
         const double weight = (ix + (ix ? -1.0 : 1.0) * (1 - (double)w[0])) * (iy + (iy ? -1.0 : 1.0) * (1 - (double)w[1])) *
                               (iz + (iz ? -1.0 : 1.0) * (1 - (double)w[2]));
-        atomic_add_t(gvol, gdt, g.at(cx, cy, cz), weight * pvol);
+        atomic_addx(gvol, gdt, g.at(cx, cy, cz), weight * pvol);
       }
 }
 
@@ -362,8 +358,8 @@ k_p2g_scatter_tiled(PGrid g, PGeom geo, PTiles pt, int axis, const void* px, int
             atomicAdd(&lmv[l], weight * m * ((double)va + cv));
           } else {                      // moved out of the tile's reach since the sort: straight to memory
             const int64_t c = g.at(cx, cy, cz);
-            atomic_add_t(gm, gdt, c, weight * m);
-            atomic_add_t(gv, gdt, c, weight * m * ((double)va + cv));
+            atomic_addx(gm, gdt, c, weight * m);
+            atomic_addx(gv, gdt, c, weight * m * ((double)va + cv));
           }
         }
   }
@@ -373,8 +369,8 @@ k_p2g_scatter_tiled(PGrid g, PGeom geo, PTiles pt, int axis, const void* px, int
     if (vm == 0.0 && vmv == 0.0) continue;
     const int lz = l % E, ly = (l / E) % E, lx = l / (E * E);
     const int64_t c = g.at(o[0] + lx, o[1] + ly, o[2] + lz);       // a touched node is inside the array (indices were clamped)
-    atomic_add_t(gm, gdt, c, vm);
-    atomic_add_t(gv, gdt, c, vmv);
+    atomic_addx(gm, gdt, c, vm);
+    atomic_addx(gv, gdt, c, vmv);
   }
 }
 
@@ -471,7 +467,7 @@ k_fluid_volume_splat_tiled(PGrid g, PGeom geo, PTiles pt, const void* px, int px
                                 (iz + (iz ? -1.0 : 1.0) * (1 - (double)w[2]));
           const int l = local_of<E>(cx, cy, cz, o);
           if (l >= 0) atomicAdd(&lv[l], weight * pvol);
-          else atomic_add_t(gvol, gdt, g.at(cx, cy, cz), weight * pvol);
+          else atomic_addx(gvol, gdt, g.at(cx, cy, cz), weight * pvol);
         }
   }
   __syncthreads();
@@ -479,7 +475,7 @@ k_fluid_volume_splat_tiled(PGrid g, PGeom geo, PTiles pt, const void* px, int px
     const double v = lv[l];
     if (v == 0.0) continue;
     const int lz = l % E, ly = (l / E) % E, lx = l / (E * E);
-    atomic_add_t(gvol, gdt, g.at(o[0] + lx, o[1] + ly, o[2] + lz), v);
+    atomic_addx(gvol, gdt, g.at(o[0] + lx, o[1] + ly, o[2] + lz), v);
   }
 }
 

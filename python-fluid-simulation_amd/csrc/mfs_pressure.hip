@@ -21,15 +21,6 @@ void set_error(const char* fmt, ...) {
 }
 
 // -------------------------------------------------------------- fractions ---
-// solver/SolidFractionCommon.py:4-16
-__device__ __forceinline__ double edge_in_fraction(double l, double r) {
-  const bool li = l < 0, ri = r < 0;
-  if (li && ri) return 1.0;
-  if (!li && !ri) return 0.0;
-  const double diff = -fabs(l - r);
-  return li ? l / diff : r / diff;
-}
-
 __device__ __forceinline__ double pick3(int i, double a, double b, double c) {
   return i == 0 ? a : (i == 1 ? b : c);
 }

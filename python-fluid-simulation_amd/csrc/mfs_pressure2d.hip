@@ -47,7 +47,7 @@ k_pressure_update2d(Grid2 g, double csx, double csy, void* vx, void* vy, int vdt
   auto axis = [&](void* vel, int64_t fi, int64_t nb, const void* w, int64_t svi, double c) {
     const double pm = ldx(lphi, ldt, nb);
     if (pc < 0 || pm < 0) {
-      const double th = fmin(1.0, fmax(0.01, edge_in_fraction2(pc, pm)));
+      const double th = fmin(1.0, fmax(0.01, edge_in_fraction(pc, pm)));
       double nv = ldx(vel, vdt, fi);
       nv += (p - ldx(pv, pdt, nb)) * c / th;
       const double ww = ldx(w, wdt, fi);

@@ -9,12 +9,12 @@
 #include <math.h>
 
 #include "mfs_common.h"
+#include "mfs_volume.h"
 
 namespace mfs {
 
 constexpr int kRenderBlock = 256;          // threads per workgroup: four waves, each an 8 x 8 pixel tile of a 16 x 16 block
 constexpr int kRenderTile = 16;            // pixels per workgroup edge
-constexpr int kMaxRenderShapes = 16;
 constexpr int kBrick = 8;                  // cells per brick edge
 constexpr int kBrickNodes = (kBrick + 1) * (kBrick + 1) * (kBrick + 1);
 // Node units by which a box is widened and a brick narrowed before a skip is computed from it.  The skips work on the line
@@ -29,20 +29,14 @@ struct RenderCamera {
   int ortho, W, H, K;
 };
 
-struct RenderShapes {                      // by value in the launch
-  const void* vol[kMaxRenderShapes];
-  const double* brick[kMaxRenderShapes];
-  int dt[kMaxRenderShapes];
-  int n[kMaxRenderShapes][3];
-  int nb[kMaxRenderShapes][3];             // bricks along each axis: ceil((n - 1) / 8)
-  double org[kMaxRenderShapes][3];
-  double h[kMaxRenderShapes];
-  double R[kMaxRenderShapes][3][3];
-  double T[kMaxRenderShapes][3];
+struct RenderBricks {                      // by value in the launch, alongside the shapes' Volumes and Poses
+  const double* brick[kMaxVolumes];        // minima per brick; null without skips
+  int nb[kMaxVolumes][3];                  // bricks along each axis: ceil((n - 1) / 8)
 };
+static_assert(sizeof(RenderBricks) == kMaxVolumes * (8 + 12), "RenderBricks: the fields, unpadded");
 
 struct RenderPalette {
-  double albedo[kMaxRenderShapes][3];
+  double albedo[kMaxVolumes][3];
   double light[3];
   int background[3];
   int n, has_light;
@@ -50,58 +44,27 @@ struct RenderPalette {
 
 #pragma clang fp contract(off)
 
-// mfs_seed.hip's seed_sample, operation by operation: shape i at the world point x is its volume sampled trilinearly at
-// R^T (x - T); outside the box: the sample at the clamped point plus the distance to the box.  inside: 0 <= u <= n - 1 on
-// all three axes, u the node coordinate; cell: the clamped cell the loads came from.  Every load is in bounds whatever x.
-__device__ __forceinline__ double render_sample(const RenderShapes& S, int i, const double x[3], bool* inside, int cell[3]) {
-  const double d[3] = {x[0] - S.T[i][0], x[1] - S.T[i][1], x[2] - S.T[i][2]};
-  int64_t c[3];
-  double f[3], e[3];
-  bool in = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double xb = (S.R[i][0][k] * d[0] + S.R[i][1][k] * d[1]) + S.R[i][2][k] * d[2];
-    const double t = (xb - S.org[i][k]) / S.h[i];
-    const double hi = (double)(S.n[i][k] - 1);
-    in = in && t >= 0.0 && t <= hi;
-    const double tc = fmin(fmax(t, 0.0), hi);
-    int ci = (int)floor(tc);
-    if (ci > S.n[i][k] - 2) ci = S.n[i][k] - 2;
-    if (ci < 0) ci = 0;                               // never taken for a finite point; keeps the loads in bounds regardless
-    c[k] = ci;
-    cell[k] = ci;
-    f[k] = tc - (double)ci;
-    e[k] = (t - tc) * S.h[i];
-  }
-  *inside = in;
-  const int64_t s0 = (int64_t)S.n[i][1] * S.n[i][2], s1 = S.n[i][2];
-  const int64_t p = c[0] * s0 + c[1] * s1 + c[2];
-  const void* v = S.vol[i];
-  const int dt = S.dt[i];
-  const double v000 = ldx(v, dt, p), v001 = ldx(v, dt, p + 1), v010 = ldx(v, dt, p + s1), v011 = ldx(v, dt, p + s1 + 1);
-  const double v100 = ldx(v, dt, p + s0), v101 = ldx(v, dt, p + s0 + 1), v110 = ldx(v, dt, p + s0 + s1),
-               v111 = ldx(v, dt, p + s0 + s1 + 1);
-  const double g0 = 1.0 - f[0], g1 = 1.0 - f[1], g2 = 1.0 - f[2];
-  const double c00 = v000 * g2 + v001 * f[2], c01 = v010 * g2 + v011 * f[2];
-  const double c10 = v100 * g2 + v101 * f[2], c11 = v110 * g2 + v111 * f[2];
-  const double c0 = c00 * g1 + c01 * f[1], c1 = c10 * g1 + c11 * f[1];
-  const double dist = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-  return (c0 * g0 + c1 * f[0]) + dist;
+// shape i at the world point x: its volume sampled at R^T (x - T) (mfs_volume.h); inside and cell as volume_sample's
+__device__ __forceinline__ double render_sample(const Volumes& V, const Poses& P, int i, const double x[3], bool* inside,
+                                                int cell[3]) {
+  double xb[3];
+  pose_to_body(P.R[i], P.T[i], x, xb);
+  return volume_sample(V, i, xb, inside, cell, nullptr);
 }
 
 // the render rule: a shape shows inside its own box only
-__device__ __forceinline__ double render_value(const RenderShapes& S, int i, const double x[3]) {
+__device__ __forceinline__ double render_value(const Volumes& V, const Poses& P, int i, const double x[3]) {
   bool inside;
   int cell[3];
-  const double v = render_sample(S, i, x, &inside, cell);
+  const double v = render_sample(V, P, i, x, &inside, cell);
   return inside ? v : INFINITY;
 }
 
 // F(x) = min over the shapes, taken with a strict < from +inf: the first shape that attains it; a NaN is passed over
-__device__ __forceinline__ double render_scene(const RenderShapes& S, int n, const double x[3]) {
+__device__ __forceinline__ double render_scene(const Volumes& V, const Poses& P, int n, const double x[3]) {
   double best = INFINITY;
   for (int i = 0; i < n; ++i) {
-    const double v = render_value(S, i, x);
+    const double v = render_value(V, P, i, x);
     if (v < best) best = v;
   }
   return best;
@@ -134,13 +97,13 @@ __device__ __forceinline__ void render_ray(const RenderCamera& C, int i, int j, 
 // decision errs towards evaluating (DESIGN.md 4.16 has the argument).
 
 // the ray in shape i's node coordinates: u(t) = u0 + t du
-__device__ __forceinline__ void render_ray_nodes(const RenderShapes& S, int i, const double o[3], const double d[3],
-                                                 double u0[3], double du[3]) {
-  const double e[3] = {o[0] - S.T[i][0], o[1] - S.T[i][1], o[2] - S.T[i][2]};
+__device__ __forceinline__ void render_ray_nodes(const Volumes& V, const Poses& P, int i, const double o[3],
+                                                 const double d[3], double u0[3], double du[3]) {
+  const double e[3] = {o[0] - P.T[i][0], o[1] - P.T[i][1], o[2] - P.T[i][2]};
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    u0[k] = (((S.R[i][0][k] * e[0] + S.R[i][1][k] * e[1]) + S.R[i][2][k] * e[2]) - S.org[i][k]) / S.h[i];
-    du[k] = ((S.R[i][0][k] * d[0] + S.R[i][1][k] * d[1]) + S.R[i][2][k] * d[2]) / S.h[i];
+    u0[k] = (((P.R[i][0][k] * e[0] + P.R[i][1][k] * e[1]) + P.R[i][2][k] * e[2]) - V.org[i][k]) / V.h[i];
+    du[k] = ((P.R[i][0][k] * d[0] + P.R[i][1][k] * d[1]) + P.R[i][2][k] * d[2]) / V.h[i];
   }
 }
 
@@ -174,14 +137,14 @@ __device__ __forceinline__ int render_index(const RenderCamera& C, double t, dou
 // The smallest sample index >= kmin of shape i that has to be evaluated, when all that is known is the shape's box: the
 // samples before the ray enters the box widened by the margin are outside the box itself, and so are all of them if the
 // ray misses the widened box or has left it before sample kmin.  One sample is given away at the entry.
-__device__ __forceinline__ int render_next_outside(const RenderCamera& C, const RenderShapes& S, int i, const double o[3],
-                                                   const double d[3], int kmin) {
+__device__ __forceinline__ int render_next_outside(const RenderCamera& C, const Volumes& V, const Poses& P, int i,
+                                                   const double o[3], const double d[3], int kmin) {
   double u0[3], du[3], lo[3], hi[3], tin, tout;
-  render_ray_nodes(S, i, o, d, u0, du);
+  render_ray_nodes(V, P, i, o, d, u0, du);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     lo[k] = -kSkipMargin;
-    hi[k] = (double)(S.n[i][k] - 1) + kSkipMargin;
+    hi[k] = (double)(V.n[i][k] - 1) + kSkipMargin;
   }
   if (!render_slab(u0, du, lo, hi, &tin, &tout)) return C.K;
   if (tout < C.near + (double)kmin * C.step) return C.K;
@@ -192,14 +155,14 @@ __device__ __forceinline__ int render_next_outside(const RenderCamera& C, const 
 // narrowed by the margin fall into cells of that brick, where a trilinear sample, a combination of the cell's nodes with
 // weights in [0, 1], cannot be negative.  Returns the first index after them (k + 1 if sample k itself is not in the
 // narrowed brick); one sample is given away at the exit.
-__device__ __forceinline__ int render_next_brick(const RenderCamera& C, const RenderShapes& S, int i, const double o[3],
-                                                 const double d[3], int k, const int cell[3]) {
+__device__ __forceinline__ int render_next_brick(const RenderCamera& C, const Volumes& V, const Poses& P, int i,
+                                                 const double o[3], const double d[3], int k, const int cell[3]) {
   double u0[3], du[3], lo[3], hi[3], tin, tout;
-  render_ray_nodes(S, i, o, d, u0, du);
+  render_ray_nodes(V, P, i, o, d, u0, du);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     const int b = cell[a] / kBrick;
-    const int end = min(kBrick * b + kBrick, S.n[i][a] - 1);
+    const int end = min(kBrick * b + kBrick, V.n[i][a] - 1);
     lo[a] = (double)(kBrick * b) + kSkipMargin;
     hi[a] = (double)end - kSkipMargin;
   }
@@ -209,11 +172,11 @@ __device__ __forceinline__ int render_next_brick(const RenderCamera& C, const Re
 }
 
 __global__ void __launch_bounds__(kRenderBlock)
-k_render_march(RenderCamera C, RenderShapes S, int n, int skip, double* __restrict__ depth, float* __restrict__ normal,
-               int* __restrict__ shape_id, int* __restrict__ steps, int* __restrict__ evals) {
+k_render_march(RenderCamera C, Volumes V, Poses P, RenderBricks B, int n, int skip, double* __restrict__ depth,
+               float* __restrict__ normal, int* __restrict__ shape_id, int* __restrict__ steps, int* __restrict__ evals) {
   // per lane and shape: the next sample index at which the shape has to be evaluated.  Each lane reads and writes its own
   // column only: no barrier.
-  __shared__ int s_next[kMaxRenderShapes][kRenderBlock];
+  __shared__ int s_next[kMaxVolumes][kRenderBlock];
   const int tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
   const int j = (int)blockIdx.x * kRenderTile + (wave & 1) * 8 + (lane & 7);
   const int i = (int)blockIdx.y * kRenderTile + (wave >> 1) * 8 + (lane >> 3);
@@ -223,7 +186,7 @@ k_render_march(RenderCamera C, RenderShapes S, int n, int skip, double* __restri
 
   int k = C.K;
   for (int s = 0; s < n; ++s) {
-    const int nx = skip ? render_next_outside(C, S, s, o, d, 0) : 0;
+    const int nx = skip ? render_next_outside(C, V, P, s, o, d, 0) : 0;
     s_next[s][tid] = nx;
     k = min(k, nx);
   }
@@ -240,15 +203,16 @@ k_render_march(RenderCamera C, RenderShapes S, int n, int skip, double* __restri
       if (nx <= k) {
         bool inside;
         int cell[3];
-        double v = render_sample(S, s, x, &inside, cell);
+        double v = render_sample(V, P, s, x, &inside, cell);
         ++count;
         nx = k + 1;
         if (!inside) {
           v = INFINITY;
-          if (skip) nx = render_next_outside(C, S, s, o, d, k + 1);
+          if (skip) nx = render_next_outside(C, V, P, s, o, d, k + 1);
         } else if (skip && !(v < 0.0)) {
-          const double m = S.brick[s][((int64_t)(cell[0] / kBrick) * S.nb[s][1] + cell[1] / kBrick) * S.nb[s][2] + cell[2] / kBrick];
-          if (m > 0.0) nx = render_next_brick(C, S, s, o, d, k, cell);
+          const int* nb = B.nb[s];
+          const double m = B.brick[s][((int64_t)(cell[0] / kBrick) * nb[1] + cell[1] / kBrick) * nb[2] + cell[2] / kBrick];
+          if (m > 0.0) nx = render_next_brick(C, V, P, s, o, d, k, cell);
         }
         s_next[s][tid] = nx;
         if (v < best) {
@@ -282,11 +246,11 @@ k_render_march(RenderCamera C, RenderShapes S, int n, int skip, double* __restri
   if (k > 0) {
     const double tp = C.near + (double)(k - 1) * C.step;
     const double xp[3] = {o[0] + tp * d[0], o[1] + tp * d[1], o[2] + tp * d[2]};
-    const double a = render_scene(S, n, xp);
+    const double a = render_scene(V, P, n, xp);
     if (a < INFINITY && a > -INFINITY) dep = (tk - C.step) + C.step * (a / (a - b));
   }
   const double xh[3] = {o[0] + dep * d[0], o[1] + dep * d[1], o[2] + dep * d[2]};
-  const double hh = 0.5 * S.h[id];
+  const double hh = 0.5 * V.h[id];
   double g[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -295,8 +259,8 @@ k_render_march(RenderCamera C, RenderShapes S, int n, int skip, double* __restri
     xb[a] = xh[a] - hh;
     bool inside;
     int cell[3];
-    const double va = render_sample(S, id, xa, &inside, cell);
-    const double vb = render_sample(S, id, xb, &inside, cell);
+    const double va = render_sample(V, P, id, xa, &inside, cell);
+    const double vb = render_sample(V, P, id, xb, &inside, cell);
     g[a] = va - vb;
   }
   const double len = sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
@@ -400,10 +364,6 @@ static int fill_render_camera(RenderCamera* C, const double* camera, int ortho, 
   return MFS_OK;
 }
 
-static bool render_extents_ok(const int64_t* e) {
-  return e[0] >= 2 && e[1] >= 2 && e[2] >= 2 && e[0] < ((int64_t)1 << 31) / e[1] / e[2];
-}
-
 }  // namespace mfs
 
 using namespace mfs;
@@ -411,14 +371,14 @@ using namespace mfs;
 extern "C" {
 
 int64_t mfs_render_brick_count3d(const int64_t extents[3]) {
-  if (!extents || !render_extents_ok(extents)) return 0;
+  if (!extents || !volume_extents_ok(extents)) return 0;
   return ((extents[0] - 2) / kBrick + 1) * ((extents[1] - 2) / kBrick + 1) * ((extents[2] - 2) / kBrick + 1);
 }
 
 int mfs_render_bricks3d(const void* volume, int dtype, const int64_t extents[3], void* bricks, mfs_stream stream) {
   MFS_REQUIRE(volume && extents && bricks, "null volume / extents / bricks");
   MFS_REQUIRE(dtype_ok(dtype), "dtype");
-  MFS_REQUIRE(render_extents_ok(extents), "volume extents must be >= 2, fewer than 2^31 nodes");
+  MFS_REQUIRE(volume_extents_ok(extents), "volume extents must be >= 2, fewer than 2^31 nodes");
   const int nb1 = (int)((extents[1] - 2) / kBrick + 1), nb2 = (int)((extents[2] - 2) / kBrick + 1);
   const int64_t blocks = mfs_render_brick_count3d(extents);
   hipLaunchKernelGGL(k_render_bricks, dim3((unsigned)blocks), dim3(kRenderBlock), 0, (hipStream_t)stream, volume, dtype,
@@ -434,40 +394,26 @@ int mfs_render_march3d(const double* camera, int ortho, int64_t width, int64_t h
                        void* shape_id, void* steps, void* evals, mfs_stream stream) {
   RenderCamera C;
   if (int st = fill_render_camera(&C, camera, ortho, width, height, near, step, num_steps)) return st;
-  MFS_REQUIRE(num_shapes >= 1 && num_shapes <= kMaxRenderShapes, "1 to 16 shapes per scene");
+  MFS_REQUIRE(num_shapes >= 1 && num_shapes <= kMaxVolumes, "1 to 16 shapes per scene");
   MFS_REQUIRE(volumes_host && dtypes_host && extents_host && origins_host && spacings_host && poses_host,
               "null shape description");
   MFS_REQUIRE(!skip || bricks_host, "null brick grids");
   MFS_REQUIRE(depth && normal && shape_id && steps, "null output");
   const int m = (int)num_shapes;
-  RenderShapes S;
-  memset(&S, 0, sizeof(S));
+  Volumes V;
+  Poses P;
+  if (int st = fill_volumes(&V, &P, m, volumes_host, dtypes_host, extents_host, origins_host, spacings_host, poses_host))
+    return st;
+  RenderBricks B;
+  memset(&B, 0, sizeof(B));
   for (int i = 0; i < m; ++i) {
-    MFS_REQUIRE(volumes_host[i], "null shape volume");
     MFS_REQUIRE(!skip || bricks_host[i], "null brick grid");
-    MFS_REQUIRE(dtype_ok(dtypes_host[i]), "dtype");
-    MFS_REQUIRE(spacings_host[i] > 0 && isfinite(spacings_host[i]), "shape volume spacing must be positive");
-    const int64_t* e = extents_host + 3 * i;
-    MFS_REQUIRE(render_extents_ok(e), "shape volume extents must be >= 2, fewer than 2^31 nodes");
-    S.vol[i] = volumes_host[i];
-    S.brick[i] = skip ? (const double*)bricks_host[i] : nullptr;
-    S.dt[i] = dtypes_host[i];
-    S.h[i] = spacings_host[i];
-    for (int k = 0; k < 3; ++k) {
-      S.n[i][k] = (int)e[k];
-      S.nb[i][k] = (int)((e[k] - 2) / kBrick + 1);
-      MFS_REQUIRE(isfinite(origins_host[3 * i + k]) && isfinite(poses_host[12 * i + 9 + k]), "shape origin / translation");
-      S.org[i][k] = origins_host[3 * i + k];
-      S.T[i][k] = poses_host[12 * i + 9 + k];
-      for (int c = 0; c < 3; ++c) {
-        MFS_REQUIRE(isfinite(poses_host[12 * i + 3 * k + c]), "shape rotation");
-        S.R[i][k][c] = poses_host[12 * i + 3 * k + c];
-      }
-    }
+    B.brick[i] = skip ? (const double*)bricks_host[i] : nullptr;
+    for (int k = 0; k < 3; ++k) B.nb[i][k] = (V.n[i][k] - 2) / kBrick + 1;
   }
   const dim3 grid((unsigned)((C.W + kRenderTile - 1) / kRenderTile), (unsigned)((C.H + kRenderTile - 1) / kRenderTile));
-  hipLaunchKernelGGL(k_render_march, grid, dim3(kRenderBlock), 0, (hipStream_t)stream, C, S, m, skip ? 1 : 0, (double*)depth,
-                     (float*)normal, (int*)shape_id, (int*)steps, (int*)evals);
+  hipLaunchKernelGGL(k_render_march, grid, dim3(kRenderBlock), 0, (hipStream_t)stream, C, V, P, B, m, skip ? 1 : 0,
+                     (double*)depth, (float*)normal, (int*)shape_id, (int*)steps, (int*)evals);
   MFS_LAUNCH_CHECK();
   return MFS_OK;
 }
@@ -478,7 +424,7 @@ int mfs_render_shade3d(const double* camera, int ortho, int64_t width, int64_t h
   RenderCamera C;
   if (int st = fill_render_camera(&C, camera, ortho, width, height, 0.0, 1.0, 1)) return st;
   MFS_REQUIRE(normal && shape_id && rgb, "null normal / shape_id / rgb");
-  MFS_REQUIRE(num_colors >= 1 && num_colors <= kMaxRenderShapes, "1 to 16 colours");
+  MFS_REQUIRE(num_colors >= 1 && num_colors <= kMaxVolumes, "1 to 16 colours");
   MFS_REQUIRE(albedo_host && background_host, "null albedo / background");
   RenderPalette P;
   memset(&P, 0, sizeof(P));

@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include "mfs_common.h"
+#include "mfs_volume.h"
 
 // separate multiply / add roundings, like the reference's expressions under CPython (the goldens)
 #pragma clang fp contract(off)
@@ -204,32 +205,18 @@ k_sdf_evaluate(const double* __restrict__ rb_d, int nrb, const void* position, i
 // from the index instead of read from an array -- get_grid_pos' rule, bound_min(f32) + (f32 index + f32 bias) * cell_size
 // in float64 with the multiply and the add rounded separately -- and EVERY vel element written (0 outside the bodies), so
 // the caller needs neither a stored position array nor a zeroing pass.  rb_w (n,3), optional: angular velocities; the
-// surface velocity of the winning body is then v + w x (pos - T), every operation rounded on its own.
-struct GridArgs3 {
-  int64_t n1, n2, total;         // extents of the two inner axes, number of points
-  double bmin[3];                // bound_min, already rounded to float32
-  float bias[3];
-  double cs[3];
-};
-
+// surface velocity of the winning body is then v + w x (pos - T), every operation rounded on its own.  The grid arguments and
+// the index split are mfs_volume.h's, shared with k_mesh_union_grid.
 __global__ void __launch_bounds__(256)
 k_sdf_evaluate_grid(const double* __restrict__ rb_d, int nrb, const double* __restrict__ rb_w, GridArgs3 a, void* sd,
                     int sdt, void* vel, int vdt) {
-  const int64_t base = (int64_t)blockIdx.x * 256;       // wave-uniform: the 64-bit divisions are per block ...
+  const int64_t base = (int64_t)blockIdx.x * 256;
   const int64_t p = base + threadIdx.x;
   if (p >= a.total) return;
-  const int64_t row = base / a.n2;
-  uint32_t i2 = (uint32_t)(base - row * a.n2) + threadIdx.x;   // ... and per thread 32-bit (extents <= 2^30)
-  const uint32_t q2 = i2 / (uint32_t)a.n2;
-  i2 -= q2 * (uint32_t)a.n2;
-  int64_t i0 = row / a.n1;
-  uint32_t i1 = (uint32_t)(row - i0 * a.n1) + q2;
-  const uint32_t q1 = i1 / (uint32_t)a.n1;
-  i1 -= q1 * (uint32_t)a.n1;
-  i0 += q1;
-  const double pos[3] = {a.bmin[0] + (double)((float)i0 + a.bias[0]) * a.cs[0],
-                         a.bmin[1] + (double)((float)i1 + a.bias[1]) * a.cs[1],
-                         a.bmin[2] + (double)((float)i2 + a.bias[2]) * a.cs[2]};
+  const LatticeIndex at = lattice_split(base, threadIdx.x, a.n1, a.n2);
+  const double pos[3] = {a.bmin[0] + (double)((float)at.i0 + a.bias[0]) * a.cs[0],
+                         a.bmin[1] + (double)((float)at.i1 + a.bias[1]) * a.cs[1],
+                         a.bmin[2] + (double)((float)at.i2 + a.bias[2]) * a.cs[2]};
   double min_sd = 100.0;
   int idx = 0;
   for (int i = 0; i < nrb; ++i) {
@@ -279,10 +266,6 @@ k_sdf_project(const double* __restrict__ rb_d, int nrb, void* position, int pdt,
 
 using namespace mfs;
 
-// evaluate_grid: per-thread index arithmetic is 32-bit within a row, the flat index 64-bit; one launch of 256-thread blocks
-static const int64_t kGridMaxExtent = (int64_t)1 << 30;
-static const int64_t kGridMaxPoints = (int64_t)0x7fffffff * 256;
-
 extern "C" {
 
 int mfs_sdf_evaluate3d(const void* rb_d, int64_t num_bodies, const void* position, int pos_dt, int64_t num_positions,
@@ -301,23 +284,11 @@ int mfs_sdf_evaluate_grid3d(const void* rb_d, int64_t num_bodies, const void* rb
                             const double bound_min[3], const double bias[3], const double cell_size[3], void* sd,
                             int sd_dt, void* vel, int vel_dt, mfs_stream stream) {
   MFS_REQUIRE(num_bodies >= 0 && num_bodies <= 4096 && (num_bodies == 0 || rb_d), "rigid bodies");
-  MFS_REQUIRE(res && bound_min && bias && cell_size, "null grid description");
-  MFS_REQUIRE(res[0] >= 0 && res[1] >= 0 && res[2] >= 0 && res[0] <= kGridMaxExtent && res[1] <= kGridMaxExtent &&
-              res[2] <= kGridMaxExtent, "grid extents");
-  MFS_REQUIRE(dtype_ok(sd_dt) && dtype_ok(vel_dt), "dtype");
-  const int64_t rows = res[0] * res[1];
-  if (rows == 0 || res[2] == 0) return MFS_OK;
-  MFS_REQUIRE(rows <= kGridMaxPoints / res[2], "grid too large for one launch");
-  MFS_REQUIRE(sd && vel, "output arrays");
   GridArgs3 a;
-  a.n1 = res[1];
-  a.n2 = res[2];
-  a.total = rows * res[2];
-  for (int k = 0; k < 3; ++k) {
-    a.bmin[k] = (double)(float)bound_min[k];
-    a.bias[k] = (float)bias[k];
-    a.cs[k] = cell_size[k];
-  }
+  if (int st = fill_grid_args(&a, res, bound_min, bias, cell_size)) return st;
+  MFS_REQUIRE(dtype_ok(sd_dt) && dtype_ok(vel_dt), "dtype");
+  if (a.total == 0) return MFS_OK;
+  MFS_REQUIRE(sd && vel, "output arrays");
   hipLaunchKernelGGL(k_sdf_evaluate_grid, dim3(cdiv(a.total, 256)), dim3(256), 0, (hipStream_t)stream,
                      (const double*)rb_d, (int)num_bodies, (const double*)rb_w, a, sd, sd_dt, vel, vel_dt);
   MFS_LAUNCH_CHECK();

@@ -7,12 +7,12 @@
 #include <math.h>
 
 #include "mfs_common.h"
+#include "mfs_volume.h"
 
 namespace mfs {
 
 constexpr int kSeedBlock = 256;            // threads per workgroup = consecutive site indices owned by it
 constexpr int kSeedWaves = kSeedBlock / kWave;
-constexpr int kMaxSeedShapes = 16;
 
 struct SeedLattice {
   int64_t n1, n2, total;     // extents of the two inner axes, number of sites
@@ -22,18 +22,8 @@ struct SeedLattice {
   uint32_t seed_lo, seed_hi;
 };
 
-struct SeedShapes {                        // by value in the launch: includes first, then excludes
-  const void* vol[kMaxSeedShapes];
-  int dt[kMaxSeedShapes];
-  int n[kMaxSeedShapes][3];
-  double org[kMaxSeedShapes][3];
-  double h[kMaxSeedShapes];
-  double R[kMaxSeedShapes][3][3];
-  double T[kMaxSeedShapes][3];
-};
-
-// Every expression below rounds as written: the position is restated in numpy bit for bit and the sampler operation by
-// operation (tests/seed_numpy.py).
+// Every expression below rounds as written: the position is restated in numpy bit for bit (tests/seed_numpy.py), as is the
+// sampler (mfs_volume.h).
 #pragma clang fp contract(off)
 
 __device__ __forceinline__ uint32_t seed_mix(uint32_t x) {
@@ -45,24 +35,9 @@ __device__ __forceinline__ uint32_t seed_mix(uint32_t x) {
   return x;
 }
 
-// site s = (i0 * n1 + i1) * n2 + i2 of the block that starts at `base`: 64-bit divisions per block, 32-bit per lane
-// (extents <= 2^30), as k_sdf_evaluate_grid
-__device__ __forceinline__ void seed_site(const SeedLattice& L, int64_t base, int tid, int64_t idx[3]) {
-  const int64_t row = base / L.n2;
-  uint32_t i2 = (uint32_t)(base - row * L.n2) + (uint32_t)tid;
-  const uint32_t q2 = i2 / (uint32_t)L.n2;
-  i2 -= q2 * (uint32_t)L.n2;
-  int64_t i0 = row / L.n1;
-  uint32_t i1 = (uint32_t)(row - i0 * L.n1) + q2;
-  const uint32_t q1 = i1 / (uint32_t)L.n1;
-  i1 -= q1 * (uint32_t)L.n1;
-  idx[0] = i0 + q1;
-  idx[1] = i1;
-  idx[2] = i2;
-}
-
 // x_a = origin_a + ((i_a + 0.5) + jitter * u_a) * h, u_a in [-0.5, 0.5) a pure function of (seed, s, a)
-__device__ __forceinline__ void seed_position(const SeedLattice& L, int64_t s, const int64_t idx[3], double x[3]) {
+__device__ __forceinline__ void seed_position(const SeedLattice& L, int64_t s, const LatticeIndex& at, double x[3]) {
+  const double idx[3] = {(double)at.i0, (double)at.i1, (double)at.i2};
   uint32_t hs = seed_mix(L.seed_lo);
   hs = seed_mix(hs ^ L.seed_hi);
   hs = seed_mix(hs ^ (uint32_t)((uint64_t)s & 0xffffffffu));
@@ -72,45 +47,17 @@ __device__ __forceinline__ void seed_position(const SeedLattice& L, int64_t s, c
     const uint32_t ha = seed_mix(hs + (uint32_t)(a + 1) * 0x9E3779B9u);
     const double u = (double)(ha >> 8) * 0x1p-24 - 0.5;
     const double ju = L.jitter * u;
-    const double c = ((double)idx[a] + 0.5) + ju;
+    const double c = (idx[a] + 0.5) + ju;
     const double ch = c * L.h;
     x[a] = L.org[a] + ch;
   }
 }
 
-// Shape i at the world point x: the body-frame point R^T (x - T) (grouped as mfs_meshsdf.hip's pose_to_body), then its
-// volume sampled trilinearly in float64 in the order of that file's volume_sample; outside the volume: the sample at the
-// clamped point plus the distance to the volume's box.
-__device__ __forceinline__ double seed_sample(const SeedShapes& S, int i, const double x[3]) {
-  const double d[3] = {x[0] - S.T[i][0], x[1] - S.T[i][1], x[2] - S.T[i][2]};
-  int64_t c[3];
-  double f[3], e[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double xb = (S.R[i][0][k] * d[0] + S.R[i][1][k] * d[1]) + S.R[i][2][k] * d[2];
-    const double t = (xb - S.org[i][k]) / S.h[i];
-    const double hi = (double)(S.n[i][k] - 1);
-    const double tc = fmin(fmax(t, 0.0), hi);
-    int ci = (int)floor(tc);
-    if (ci > S.n[i][k] - 2) ci = S.n[i][k] - 2;
-    if (ci < 0) ci = 0;                               // never taken for a finite point; keeps the loads in bounds regardless
-    c[k] = ci;
-    f[k] = tc - (double)ci;
-    e[k] = (t - tc) * S.h[i];
-  }
-  const int64_t s0 = (int64_t)S.n[i][1] * S.n[i][2], s1 = S.n[i][2];
-  const int64_t p = c[0] * s0 + c[1] * s1 + c[2];
-  const void* v = S.vol[i];
-  const int dt = S.dt[i];
-  const double v000 = ldx(v, dt, p), v001 = ldx(v, dt, p + 1), v010 = ldx(v, dt, p + s1), v011 = ldx(v, dt, p + s1 + 1);
-  const double v100 = ldx(v, dt, p + s0), v101 = ldx(v, dt, p + s0 + 1), v110 = ldx(v, dt, p + s0 + s1),
-               v111 = ldx(v, dt, p + s0 + s1 + 1);
-  const double g0 = 1.0 - f[0], g1 = 1.0 - f[1], g2 = 1.0 - f[2];
-  const double c00 = v000 * g2 + v001 * f[2], c01 = v010 * g2 + v011 * f[2];
-  const double c10 = v100 * g2 + v101 * f[2], c11 = v110 * g2 + v111 * f[2];
-  const double c0 = c00 * g1 + c01 * f[1], c1 = c10 * g1 + c11 * f[1];
-  const double dist = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-  return (c0 * g0 + c1 * f[0]) + dist;
+// shape i at the world point x: its volume sampled at the body-frame point R^T (x - T)
+__device__ __forceinline__ double seed_sample(const Volumes& V, const Poses& P, int i, const double x[3]) {
+  double xb[3];
+  pose_to_body(P.R[i], P.T[i], x, xb);
+  return volume_sample(V, i, xb);
 }
 
 // minimum that keeps a NaN once it has seen one (numpy's np.minimum): a NaN sample then fails both comparisons below
@@ -120,7 +67,7 @@ __device__ __forceinline__ double seed_min(double m, double d) { return (d < m |
 // includes keep the site: the decision is the same, and most of a lattice is outside the liquid.
 // counts (may be null): per workgroup, the number kept; masks (may be null): per workgroup, the four waves' ballots.
 __global__ void __launch_bounds__(kSeedBlock)
-k_seed_count(SeedLattice L, SeedShapes S, int n_inc, int n_exc, double clearance, int* __restrict__ counts,
+k_seed_count(SeedLattice L, Volumes V, Poses P, int n_inc, int n_exc, double clearance, int* __restrict__ counts,
              unsigned long long* __restrict__ masks) {
   __shared__ int s_wave[kSeedWaves];
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
@@ -128,15 +75,13 @@ k_seed_count(SeedLattice L, SeedShapes S, int n_inc, int n_exc, double clearance
   const int64_t s = base + tid;
   bool keep = false;
   if (s < L.total) {
-    int64_t idx[3];
     double x[3];
-    seed_site(L, base, tid, idx);
-    seed_position(L, s, idx, x);
+    seed_position(L, s, lattice_split(base, tid, L.n1, L.n2), x);
     double inc = INFINITY;
-    for (int i = 0; i < n_inc; ++i) inc = seed_min(inc, seed_sample(S, i, x));
+    for (int i = 0; i < n_inc; ++i) inc = seed_min(inc, seed_sample(V, P, i, x));
     if (inc < 0.0) {
       double exc = INFINITY;
-      for (int i = n_inc; i < n_inc + n_exc; ++i) exc = seed_min(exc, seed_sample(S, i, x));
+      for (int i = n_inc; i < n_inc + n_exc; ++i) exc = seed_min(exc, seed_sample(V, P, i, x));
       keep = exc > clearance;
     }
   }
@@ -174,10 +119,8 @@ k_seed_fill(SeedLattice L, const unsigned long long* __restrict__ masks, const i
   if (!((mine >> lane) & 1ull) || s >= L.total) return;
   const int64_t row = offsets[blockIdx.x] + before + __popcll(mine & ((1ull << lane) - 1ull));
   if (row < 0 || row >= capacity) return;
-  int64_t idx[3];
   double x[3];
-  seed_site(L, base, tid, idx);
-  seed_position(L, s, idx, x);
+  seed_position(L, s, lattice_split(base, tid, L.n1, L.n2), x);
   for (int a = 0; a < 3; ++a) stx(px, pdt, 3 * row + a, x[a]);
   if (sites) sites[row] = s;
 }
@@ -226,39 +169,20 @@ int mfs_seed_count3d(const int64_t shape[3], const double origin[3], double spac
                      const double* poses_host, double clearance, void* counts, void* masks, mfs_stream stream) {
   SeedLattice L;
   if (int st = fill_seed_lattice(&L, shape, origin, spacing, jitter, seed)) return st;
-  MFS_REQUIRE(num_include >= 0 && num_exclude >= 0 && num_include <= kMaxSeedShapes &&
-              num_exclude <= kMaxSeedShapes - num_include, "at most 16 shapes per call");
+  MFS_REQUIRE(num_include >= 0 && num_exclude >= 0 && num_include <= kMaxVolumes &&
+              num_exclude <= kMaxVolumes - num_include, "at most 16 shapes per call");
   MFS_REQUIRE(num_include >= 1, "at least one include shape");
   MFS_REQUIRE(volumes_host && dtypes_host && extents_host && origins_host && spacings_host && poses_host,
               "null shape description");
   MFS_REQUIRE(!(clearance != clearance), "clearance is NaN");
   MFS_REQUIRE(counts || masks, "null counts and masks");
   const int m = (int)(num_include + num_exclude);
-  SeedShapes S;
-  memset(&S, 0, sizeof(S));
-  for (int i = 0; i < m; ++i) {
-    MFS_REQUIRE(volumes_host[i], "null shape volume");
-    MFS_REQUIRE(dtype_ok(dtypes_host[i]), "dtype");
-    MFS_REQUIRE(spacings_host[i] > 0 && isfinite(spacings_host[i]), "shape volume spacing must be positive");
-    const int64_t* e = extents_host + 3 * i;
-    MFS_REQUIRE(e[0] >= 2 && e[1] >= 2 && e[2] >= 2 && e[0] < ((int64_t)1 << 31) / e[1] / e[2],
-                "shape volume extents must be >= 2, fewer than 2^31 nodes");
-    S.vol[i] = volumes_host[i];
-    S.dt[i] = dtypes_host[i];
-    S.h[i] = spacings_host[i];
-    for (int k = 0; k < 3; ++k) {
-      S.n[i][k] = (int)e[k];
-      MFS_REQUIRE(isfinite(origins_host[3 * i + k]) && isfinite(poses_host[12 * i + 9 + k]), "shape origin / translation");
-      S.org[i][k] = origins_host[3 * i + k];
-      S.T[i][k] = poses_host[12 * i + 9 + k];
-      for (int c = 0; c < 3; ++c) {
-        MFS_REQUIRE(isfinite(poses_host[12 * i + 3 * k + c]), "shape rotation");
-        S.R[i][k][c] = poses_host[12 * i + 3 * k + c];
-      }
-    }
-  }
+  Volumes V;
+  Poses P;
+  if (int st = fill_volumes(&V, &P, m, volumes_host, dtypes_host, extents_host, origins_host, spacings_host, poses_host))
+    return st;
   const int64_t blocks = (L.total + kSeedBlock - 1) / kSeedBlock;
-  hipLaunchKernelGGL(k_seed_count, dim3((unsigned)blocks), dim3(kSeedBlock), 0, (hipStream_t)stream, L, S,
+  hipLaunchKernelGGL(k_seed_count, dim3((unsigned)blocks), dim3(kSeedBlock), 0, (hipStream_t)stream, L, V, P,
                      (int)num_include, (int)num_exclude, clearance, (int*)counts, (unsigned long long*)masks);
   MFS_LAUNCH_CHECK();
   return MFS_OK;

@@ -7,6 +7,7 @@
 #include <math.h>
 
 #include "mfs_common.h"
+#include "mfs_volume.h"
 
 namespace mfs {
 
@@ -139,12 +140,8 @@ k_skin_field(SkinLattice L, float r, float R, float inv_R2, float background, co
 }
 
 static int fill_skin_lattice(SkinLattice* L, const int64_t shape[3], const double origin[3], double spacing) {
-  MFS_REQUIRE(shape && origin, "null lattice description");
-  MFS_REQUIRE(shape[0] >= 2 && shape[1] >= 2 && shape[2] >= 2, "lattice extents must be >= 2");
-  MFS_REQUIRE(shape[0] < ((int64_t)1 << 31) / shape[1] / shape[2], "lattice node count must stay below 2^31");
-  MFS_REQUIRE(spacing > 0 && isfinite(spacing), "spacing must be positive");
+  if (int st = check_lattice(shape, origin, spacing)) return st;
   for (int k = 0; k < 3; ++k) {
-    MFS_REQUIRE(isfinite(origin[k]), "origin must be finite");
     L->n[k] = (int)shape[k];
     L->org[k] = origin[k];
   }

@@ -23,9 +23,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import _lib
-from . import seed as _seed
-from . import tensors as T
+from . import _lib, seed as _seed, tensors as T, volumes as _volumes
 
 MAX_SHAPES = 16                         # the shapes' descriptions travel by value in the launch
 MAX_EXTENT = 16384                      # pixels per image axis
@@ -147,31 +145,9 @@ def _shapes(shapes, device=True):
     out = _seed._shape_list(shapes)
     if not (1 <= len(out) <= MAX_SHAPES):
         raise ValueError(f"{len(out)} shapes: a scene has 1 .. {MAX_SHAPES}")
-    for k, s in enumerate(out):
-        name = f"shape[{k}]"
-        phi = s.volume.phi
-        if not isinstance(phi, torch.Tensor):
-            raise TypeError(f"{name}.phi: expected a torch tensor on the GPU, got {type(phi).__name__}")
-        if phi.dim() != 3 or min(phi.shape) < 2 or phi.numel() > 2 ** 31 - 1:
-            raise ValueError(f"{name}.phi: expected a volume (n0, n1, n2), every extent >= 2, fewer than 2^31 nodes, got "
-                             f"{tuple(phi.shape)}")
-        if phi.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"{name}.phi: dtype {phi.dtype} unsupported (float32 / float64)")
-        if not phi.is_contiguous():
-            raise ValueError(f"{name}.phi: tensor must be C-contiguous")
-        h = float(s.volume.spacing)
-        if not (math.isfinite(h) and h > 0):
-            raise ValueError(f"{name}.spacing must be positive, got {h}")
-        if not (all(math.isfinite(v) for v in T.as_f64_list(s.volume.origin, 3)) and np.isfinite(s.T).all()
-                and np.isfinite(s.R).all()):
-            raise ValueError(f"{name}: origin and pose must be finite")
-    for k, s in enumerate(out if device else ()):
-        phi = s.volume.phi
-        if not phi.is_cuda:
-            raise TypeError(f"shape {k}: volume is on {phi.device}; rendering runs on the GPU only (no CPU fallback)")
-        if phi.device != out[0].volume.phi.device:
-            raise ValueError(f"shape {k}: volume is on {phi.device}, shape 0 on {out[0].volume.phi.device}; all volumes must "
-                             "be on one device")
+    _volumes.check_shapes(out, [f"shape[{k}]" for k in range(len(out))])
+    if device:
+        _volumes.check_one_gpu(out, "rendering")
     return out
 
 
@@ -225,25 +201,17 @@ class Scene:
         W, H = camera.width, camera.height
         lib = _lib.load()
         m, dev = len(self.shapes), self.device
-        vols, grids, dts, ext, orgs, sps, poses = (ctypes.c_void_p * m)(), (ctypes.c_void_p * m)(), [], [], [], [], []
-        for i, s in enumerate(self.shapes):
-            phi = s.volume.phi
-            vols[i], grids[i] = phi.data_ptr(), self.bricks[i].data_ptr()
-            dts.append(T.code(phi))
-            ext += [int(v) for v in phi.shape]
-            orgs += T.as_f64_list(s.volume.origin, 3)
-            sps.append(float(s.volume.spacing))
-            poses += [float(v) for v in s.R.reshape(-1)] + [float(v) for v in s.T]
+        grids = (ctypes.c_void_p * m)(*[g.data_ptr() for g in self.bricks])
         with torch.cuda.device(dev):
             depth = torch.empty((H, W), dtype=torch.float64, device=dev)
             normal = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
             ident = torch.empty((H, W), dtype=torch.int32, device=dev)
             steps = torch.empty((H, W), dtype=torch.int32, device=dev)
             evals = torch.empty((H, W), dtype=torch.int32, device=dev) if stats is not None else None
-            _lib.check(lib.mfs_render_march3d(_lib.f64x(camera.packed()), int(camera.ortho), W, H, near, step, K, m, vols,
-                                              (ctypes.c_int * m)(*dts), _lib.i64x(ext), _lib.f64x(orgs), _lib.f64x(sps),
-                                              _lib.f64x(poses), grids, int(bool(skip)), T.ptr(depth), T.ptr(normal),
-                                              T.ptr(ident), T.ptr(steps), None if evals is None else T.ptr(evals), T.stream()),
+            _lib.check(lib.mfs_render_march3d(_lib.f64x(camera.packed()), int(camera.ortho), W, H, near, step, K, m,
+                                              *_volumes.pack_shapes(self.shapes), grids, int(bool(skip)), T.ptr(depth),
+                                              T.ptr(normal), T.ptr(ident), T.ptr(steps),
+                                              None if evals is None else T.ptr(evals), T.stream()),
                        "mfs_render_march3d")
             if stats is not None:
                 stats.update(pixels=W * H, hits=int((steps >= 0).sum().item()),

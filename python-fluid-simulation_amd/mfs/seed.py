@@ -11,14 +11,12 @@ no array of candidates, and two calls return the same bits.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
 import torch
 
-from . import _lib
-from . import tensors as T
+from . import _lib, tensors as T, volumes as _volumes
 
 MAX_SHAPES = 16                         # the shapes' descriptions travel by value in the launch
 MAX_EXTENT = 2 ** 30                    # per axis of the site lattice
@@ -101,31 +99,8 @@ def _arguments(include, shape, origin, spacing, exclude, clearance, jitter, seed
     if len(inc) + len(exc) > MAX_SHAPES:
         raise ValueError(f"{len(inc)} include + {len(exc)} exclude shapes: at most {MAX_SHAPES} per call")
     shapes = inc + exc
-    for k, s in enumerate(shapes):
-        name = f"{'include' if k < len(inc) else 'exclude'}[{k if k < len(inc) else k - len(inc)}]"
-        phi = s.volume.phi
-        if not isinstance(phi, torch.Tensor):
-            raise TypeError(f"{name}.phi: expected a torch tensor on the GPU, got {type(phi).__name__}")
-        if phi.dim() != 3 or min(phi.shape) < 2 or phi.numel() > 2 ** 31 - 1:
-            raise ValueError(f"{name}.phi: expected a volume (n0, n1, n2), every extent >= 2, fewer than 2^31 nodes, got "
-                             f"{tuple(phi.shape)}")
-        if phi.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"{name}.phi: dtype {phi.dtype} unsupported (float32 / float64)")
-        if not phi.is_contiguous():
-            raise ValueError(f"{name}.phi: tensor must be C-contiguous")
-        h = float(s.volume.spacing)
-        if not (math.isfinite(h) and h > 0):
-            raise ValueError(f"{name}.spacing must be positive, got {h}")
-        if not (all(math.isfinite(v) for v in T.as_f64_list(s.volume.origin, 3)) and np.isfinite(s.T).all()
-                and np.isfinite(s.R).all()):
-            raise ValueError(f"{name}: origin and pose must be finite")
-    for k, s in enumerate(shapes):
-        phi = s.volume.phi
-        if not phi.is_cuda:
-            raise TypeError(f"shape {k}: volume is on {phi.device}; seeding runs on the GPU only (no CPU fallback)")
-        if phi.device != shapes[0].volume.phi.device:
-            raise ValueError(f"shape {k}: volume is on {phi.device}, shape 0 on {shapes[0].volume.phi.device}; all volumes "
-                             "must be on one device")
+    _volumes.check_shapes(shapes, [f"include[{k}]" for k in range(len(inc))] + [f"exclude[{k}]" for k in range(len(exc))])
+    _volumes.check_one_gpu(shapes, "seeding")
     return shapes, len(inc), len(exc), shape, org, spacing, clearance, jitter, int(seed)
 
 
@@ -133,23 +108,12 @@ def _count(lib, a, masks_wanted):
     """launch the count pass; returns (counts int32, masks or None, the lattice's ctypes triple)"""
     shapes, n_inc, n_exc, shape, org, spacing, clearance, jitter, seed = a
     dev = shapes[0].volume.phi.device
-    m = len(shapes)
-    vols, dts, ext, orgs, sps, poses = (ctypes.c_void_p * m)(), [], [], [], [], []
-    for i, s in enumerate(shapes):
-        phi = s.volume.phi
-        vols[i] = phi.data_ptr()
-        dts.append(T.code(phi))
-        ext += [int(v) for v in phi.shape]
-        orgs += T.as_f64_list(s.volume.origin, 3)
-        sps.append(float(s.volume.spacing))
-        poses += [float(v) for v in s.R.reshape(-1)] + [float(v) for v in s.T]
     g, o = _lib.i64x(shape), _lib.f64x(org)
     blocks = int(lib.mfs_seed_blocks3d(g))
     counts = torch.empty(blocks, dtype=torch.int32, device=dev)
     masks = torch.empty((blocks, 4), dtype=torch.int64, device=dev) if masks_wanted else None
-    _lib.check(lib.mfs_seed_count3d(g, o, spacing, jitter, seed, n_inc, n_exc, vols, (ctypes.c_int * m)(*dts), _lib.i64x(ext),
-                                    _lib.f64x(orgs), _lib.f64x(sps), _lib.f64x(poses), clearance, T.ptr(counts),
-                                    None if masks is None else T.ptr(masks), T.stream()), "mfs_seed_count3d")
+    _lib.check(lib.mfs_seed_count3d(g, o, spacing, jitter, seed, n_inc, n_exc, *_volumes.pack_shapes(shapes), clearance,
+                                    T.ptr(counts), None if masks is None else T.ptr(masks), T.stream()), "mfs_seed_count3d")
     return counts, masks, (g, o)
 
 

@@ -4,13 +4,12 @@ description (`generate_rb`, `transform_rb`, `set_vel_rb`, `get_T`, `get_R` -- ho
 body velocity at a set of points; ipynb scene set-up) and `project` (push particles out of / into
 the bodies; ipynb:4584, every step).  PyTorch-ROCm tensors, HIP kernels behind the C ABI; no CPU path.
 """
-import ctypes
 
 import numpy as np
 import torch
 from scipy.spatial.transform import Rotation as R
 
-from mfs import _lib, tensors as T
+from mfs import _lib, tensors as T, volumes as _volumes
 
 
 def get_T(position):
@@ -169,16 +168,13 @@ def _mesh_volumes(rb, bodies):
         raise ValueError(f"{m} mesh bodies: at most {MAX_MESH_BODIES} per call")
     if int(rb.shape[0]) != m:
         raise ValueError(f"mesh_rb has {int(rb.shape[0])} rows for {m} mesh bodies")
-    vols, ext, org, sp = (ctypes.c_void_p * max(m, 1))(), [], [], []
-    for i, b in enumerate(bodies):
+    vols = []
+    for b in bodies:
         phi = T.dev(b.sdf.phi, "sdf.phi")
         if phi.dtype != torch.float32 or phi.dim() != 3 or phi.device != rb.device:
             raise ValueError("mesh body volume: expected a float32 (n0, n1, n2) tensor on mesh_rb's device")
-        vols[i] = phi.data_ptr()
-        ext += [int(v) for v in phi.shape]
-        org += T.as_f64_list(b.sdf.origin, 3)
-        sp.append(float(b.sdf.spacing))
-    return rb, m, (vols, _lib.i64x(ext or [0]), _lib.f64x(org or [0.0]), _lib.f64x(sp or [0.0]))
+        vols.append((phi, b.sdf.origin, b.sdf.spacing))
+    return rb, m, _volumes.pack(vols, dtypes=False)                      # no poses either: the kernels read mesh_rb
 
 
 def union_mesh_grid(mesh_rb, bodies, sd, vel, bound_min, cell_size, bias, rb_w=None):
