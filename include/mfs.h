@@ -889,6 +889,45 @@ int mfs_render_shade3d(const double* camera, int ortho, int64_t width, int64_t h
                        const void* shape_id, int64_t num_colors, const double* albedo_host, const int* background_host,
                        const double* light_host, void* rgb, mfs_stream stream);
 
+/* Paths: shadows, a refracting liquid, supersampling (tests/render_paths_numpy.py restates every operation).  Additions:
+ * the ABI version stays.
+ * _bricks_max3d: as _bricks3d, the MAXIMUM over each brick's nodes, +inf if one of them is NaN.
+ * _paths3d: one ray per pixel of the width x height image (for s x s supersampling pass s times the extents and the
+ * same camera: half_w and half_h do not change).  A segment march generalises the march above to any ray and a medium:
+ * samples x_k = o + (t0 + k step) d, t0 = near for the camera's ray and 0 for every later segment; in air the rule is
+ * the one above, over the shapes the segment includes; inside shape m (the medium) shape m counts negated and -inf outside
+ * its box, so the hit with id m is the exit.  The normal is the hit shape's un-negated central difference, in float64.
+ * materials_host: num_shapes x 8 HOST doubles: kind (0 opaque, 1 liquid), colour r g b in 0 .. 1, ior in (1, 4], absorb
+ * r g b >= 0 per world unit (the last four are read of a liquid only).  light_host: 3 HOST doubles, the unit vector
+ * towards a directional light; null: l = -d of the camera's ray.  background_host: 3 HOST ints in 0 .. 255, bg = value / 255.
+ * A path runs at most four marches in fixed slots: 0 the camera's ray (num_steps samples); 1 inside the liquid
+ * (inside_steps); 2 after the exit (num_steps); 3 the shadow ray of the surface finally shaded (shadow_steps, over the
+ * opaque shapes only; run iff shadows != 0).  Slot 0 misses: bg.  A surface finally shaded (an opaque shape in slot 0, 1
+ * or 2, or any shape met in slot 2, or another liquid met in slot 1) at x with normal n gives
+ * albedo * (0.25 + 0.75 * (vis * max(0, n32 . l))), n32 = n rounded to float32 as _march3d stores it, vis = 0 if the
+ * shadow march from x + bias n along l hits, else 1.  A liquid hit in slot 0: n faces the ray (negated if d . n > 0),
+ * c = -d . n, r0 = ((ior - 1) / (ior + 1))^2, R = r0 + (1 - r0) (1 - c)^5 by multiplications; eta = 1 / ior,
+ * k = 1 - eta^2 (1 - c^2), t = eta d + (eta c - sqrt(k)) n, normalised; slot 1 starts at x - bias n along t.  Its miss
+ * leaves the liquid's colour behind, with L = inside_steps * step; a surface met leaves its shaded colour, with L = the
+ * segment's depth; the exit (id = the medium, L = depth) refracts the same way with eta = ior and n facing the ray:
+ * k < 0 is total internal reflection and leaves the liquid's colour, otherwise slot 2 starts at x - bias n; its miss
+ * leaves bg.  colour = R bg + ((1 - R) exp(-(absorb L))) behind.
+ * Outputs (DEVICE, C order): color height x width x 3 float64; steps and shape_id height x width x 4 int32 per slot
+ * (-2: slot not run, -1: a miss); length height x width float64 (L; 0 without a liquid hit); evals (may be null) int32.
+ * bricks_max_host[i]: read for liquid shapes only.  skip == 0 gives the same bits in every output but evals.
+ * _resolve3d: rgb (DEVICE, height x width x 3 uint8) from color (DEVICE, (samples height) x (samples width) x 3 float64):
+ * the samples^2 colours of a pixel summed in row-major order, divided by samples^2, floor(255 c + 0.5) held in 0 .. 255;
+ * samples in 1 .. 4.                                                                                              */
+int mfs_render_bricks_max3d(const void* volume, int dtype, const int64_t extents[3], void* bricks, mfs_stream stream);
+int mfs_render_paths3d(const double* camera, int ortho, int64_t width, int64_t height, double near, double step,
+                       int64_t num_steps, int64_t num_shapes, const void* const* volumes_host, const int* dtypes_host,
+                       const int64_t* extents_host, const double* origins_host, const double* spacings_host,
+                       const double* poses_host, const void* const* bricks_host, const void* const* bricks_max_host,
+                       int skip, const double* materials_host, const double* light_host, const int* background_host,
+                       int shadows, double bias, int64_t shadow_steps, int64_t inside_steps, void* color, void* steps,
+                       void* shape_id, void* length, void* evals, mfs_stream stream);
+int mfs_render_resolve3d(const void* color, int64_t width, int64_t height, int samples, void* rgb, mfs_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,11 +1,14 @@
 // mfs_render.hip -- ray-marched images of level-set volumes on gfx950 (no reference counterpart):
 //   k_render_bricks  one workgroup per brick of 8 x 8 x 8 cells (9^3 nodes, clipped at the volume's end): its minimum,
-//                    -inf when it holds a NaN; wave reduction, no atomics
+//                    -inf when it holds a NaN (or its maximum, +inf); wave reduction, no atomics
 //   k_render_march   one lane per pixel, one wave per 8 x 8 pixel tile: walks the samples t_k = near + k * step of its ray,
 //                    stops at the first with min over the shapes < 0, refines by one secant step, takes the normal
 //   k_render_shade   Lambert from the normals and shape ids, one lane per pixel
+//   k_render_paths   one lane per sub-pixel ray: up to four such marches in a loop over the path's state -- the camera's
+//                    ray, inside a refracting liquid, after the exit, the shadow ray -- and the path's colour
+//   k_render_resolve the box filter of the sub-pixel colours and the byte conversion
 // Every shape is a sampled signed field under a rigid pose, as in mfs_seed.hip; the arithmetic on the ray is float64 with
-// contraction off and is restated in numpy operation by operation (tests/render_numpy.py).
+// contraction off and is restated in numpy operation by operation (tests/render_numpy.py, tests/render_paths_numpy.py).
 #include <math.h>
 
 #include "mfs_common.h"
@@ -126,9 +129,16 @@ __device__ __forceinline__ bool render_slab(const double u0[3], const double du[
   return a <= b;
 }
 
-// floor((t - near) / step) + shift as a sample index, held in [lo, K]
-__device__ __forceinline__ int render_index(const RenderCamera& C, double t, double shift, int lo) {
-  double q = floor((t - C.near) / C.step) + shift;
+// The samples of one march: t_k = t0 + k * step, k < K.  The camera's rays start at t0 = near, every later segment of a
+// path at its own origin with t0 = 0.
+struct RenderSeg {
+  double t0, step;
+  int K;
+};
+
+// floor((t - t0) / step) + shift as a sample index, held in [lo, K]
+__device__ __forceinline__ int render_index(const RenderSeg& C, double t, double shift, int lo) {
+  double q = floor((t - C.t0) / C.step) + shift;
   if (!(q > (double)lo)) return lo;                   // also a NaN
   if (q > (double)C.K) return C.K;
   return (int)q;
@@ -137,7 +147,7 @@ __device__ __forceinline__ int render_index(const RenderCamera& C, double t, dou
 // The smallest sample index >= kmin of shape i that has to be evaluated, when all that is known is the shape's box: the
 // samples before the ray enters the box widened by the margin are outside the box itself, and so are all of them if the
 // ray misses the widened box or has left it before sample kmin.  One sample is given away at the entry.
-__device__ __forceinline__ int render_next_outside(const RenderCamera& C, const Volumes& V, const Poses& P, int i,
+__device__ __forceinline__ int render_next_outside(const RenderSeg& C, const Volumes& V, const Poses& P, int i,
                                                    const double o[3], const double d[3], int kmin) {
   double u0[3], du[3], lo[3], hi[3], tin, tout;
   render_ray_nodes(V, P, i, o, d, u0, du);
@@ -147,15 +157,16 @@ __device__ __forceinline__ int render_next_outside(const RenderCamera& C, const 
     hi[k] = (double)(V.n[i][k] - 1) + kSkipMargin;
   }
   if (!render_slab(u0, du, lo, hi, &tin, &tout)) return C.K;
-  if (tout < C.near + (double)kmin * C.step) return C.K;
+  if (tout < C.t0 + (double)kmin * C.step) return C.K;
   return render_index(C, tin, -1.0, kmin);
 }
 
 // Sample k of shape i lies in the brick of `cell`, whose minimum is > 0: the samples up to the ray's exit from the brick
 // narrowed by the margin fall into cells of that brick, where a trilinear sample, a combination of the cell's nodes with
-// weights in [0, 1], cannot be negative.  Returns the first index after them (k + 1 if sample k itself is not in the
+// weights in [0, 1], cannot be negative.  (Inside the shape, where its value counts negated, the same holds of a brick
+// whose maximum is < 0: the sample cannot be positive.)  Returns the first index after them (k + 1 if sample k itself is not in the
 // narrowed brick); one sample is given away at the exit.
-__device__ __forceinline__ int render_next_brick(const RenderCamera& C, const Volumes& V, const Poses& P, int i,
+__device__ __forceinline__ int render_next_brick(const RenderSeg& C, const Volumes& V, const Poses& P, int i,
                                                  const double o[3], const double d[3], int k, const int cell[3]) {
   double u0[3], du[3], lo[3], hi[3], tin, tout;
   render_ray_nodes(V, P, i, o, d, u0, du);
@@ -167,7 +178,7 @@ __device__ __forceinline__ int render_next_brick(const RenderCamera& C, const Vo
     hi[a] = (double)end - kSkipMargin;
   }
   if (!render_slab(u0, du, lo, hi, &tin, &tout)) return k + 1;
-  if (!(tin <= C.near + (double)k * C.step)) return k + 1;
+  if (!(tin <= C.t0 + (double)k * C.step)) return k + 1;
   return render_index(C, tout, 0.0, k + 1);
 }
 
@@ -183,10 +194,11 @@ k_render_march(RenderCamera C, Volumes V, Poses P, RenderBricks B, int n, int sk
   if (i >= C.H || j >= C.W) return;
   double o[3], d[3];
   render_ray(C, i, j, o, d);
+  const RenderSeg G = {C.near, C.step, C.K};
 
   int k = C.K;
   for (int s = 0; s < n; ++s) {
-    const int nx = skip ? render_next_outside(C, V, P, s, o, d, 0) : 0;
+    const int nx = skip ? render_next_outside(G, V, P, s, o, d, 0) : 0;
     s_next[s][tid] = nx;
     k = min(k, nx);
   }
@@ -208,11 +220,11 @@ k_render_march(RenderCamera C, Volumes V, Poses P, RenderBricks B, int n, int sk
         nx = k + 1;
         if (!inside) {
           v = INFINITY;
-          if (skip) nx = render_next_outside(C, V, P, s, o, d, k + 1);
+          if (skip) nx = render_next_outside(G, V, P, s, o, d, k + 1);
         } else if (skip && !(v < 0.0)) {
           const int* nb = B.nb[s];
           const double m = B.brick[s][((int64_t)(cell[0] / kBrick) * nb[1] + cell[1] / kBrick) * nb[2] + cell[2] / kBrick];
-          if (m > 0.0) nx = render_next_brick(C, V, P, s, o, d, k, cell);
+          if (m > 0.0) nx = render_next_brick(G, V, P, s, o, d, k, cell);
         }
         s_next[s][tid] = nx;
         if (v < best) {
@@ -272,6 +284,255 @@ k_render_march(RenderCamera C, Volumes V, Poses P, RenderBricks B, int n, int sk
   steps[p] = k;
 }
 
+// ---- paths: shadows, one refracting liquid interface pair, supersampling (tests/render_paths_numpy.py restates all of it)
+
+struct RenderBrickPtrs {                   // the brick counts follow from the extents: (n - 2) / 8 + 1
+  const double* lo[kMaxVolumes];           // minima per brick; null without skips
+  const double* hi[kMaxVolumes];           // maxima per brick, of the liquid shapes only; null elsewhere
+};
+
+struct RenderLook {
+  double albedo[kMaxVolumes][3];
+  double absorb[kMaxVolumes][3];           // per world unit, of a liquid
+  double ior[kMaxVolumes];                 // 0: opaque
+  double light[3], background[3];
+  double bias;
+  int has_light, shadows, K_shadow, K_inside;
+  unsigned opaque;                         // bit s: shape s is opaque
+  int pad_;
+};
+static_assert(sizeof(RenderCamera) + sizeof(Volumes) + sizeof(Poses) + sizeof(RenderBrickPtrs) + sizeof(RenderLook) + 64 <= 4096,
+              "k_render_paths: the launch arguments must fit the 4 KiB kernel argument segment");
+
+// One lane per sub-pixel ray, one wave per 8 x 8 tile.  A path is at most four marches in fixed slots -- 0 primary, 1 inside
+// the liquid, 2 after the exit, 3 the shadow ray of the surface finally shaded -- run by ONE march in a loop over the
+// path's state (o, d, segment, medium, mask).  medium = m: shape m counts negated, -inf outside its box; a shape whose
+// bit is clear in mask is never sampled.
+__global__ void __launch_bounds__(kRenderBlock)
+k_render_paths(RenderCamera C, Volumes V, Poses P, RenderBrickPtrs B, RenderLook L, int n, int skip,
+               double* __restrict__ color, int* __restrict__ steps, int* __restrict__ shape_id, double* __restrict__ length,
+               int* __restrict__ evals) {
+  __shared__ int s_next[kMaxVolumes][kRenderBlock];   // as k_render_march's: each lane its own column, no barrier
+  // The Fresnel term and the length inside the liquid wait here, not in registers, while the later marches run: with
+  // them the kernel fits 256 VGPRs, two waves per SIMD as k_render_march.  Each lane its own column again.
+  __shared__ double s_keep[2][kRenderBlock];
+  const int tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
+  const int j = (int)blockIdx.x * kRenderTile + (wave & 1) * 8 + (lane & 7);
+  const int i = (int)blockIdx.y * kRenderTile + (wave >> 1) * 8 + (lane >> 3);
+  if (i >= C.H || j >= C.W) return;
+  s_keep[0][tid] = s_keep[1][tid] = 0.0;
+  const int64_t p = (int64_t)i * C.W + j;
+  double o[3], d[3];
+  render_ray(C, i, j, o, d);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) steps[4 * p + q] = shape_id[4 * p + q] = -2;
+
+  int K = C.K;                                        // of the segment in hand
+  unsigned mask = n >= 32 ? ~0u : (1u << n) - 1u;
+  int medium = -1, slot = 0, liq = -1, sid = -1, count = 0;
+  bool lit = true, own = false;                       // own: the liquid's own colour lies behind it, not the background
+  double lam = 0.0;
+
+  for (;;) {                                          // at most four passes: the slot only grows
+    const RenderSeg G = {slot == 0 ? C.near : 0.0, C.step, K};
+    int k = G.K;
+    for (int s = 0; s < n; ++s) {
+      int nx = G.K;
+      if ((mask >> s) & 1u) nx = (skip && s != medium) ? render_next_outside(G, V, P, s, o, d, 0) : 0;
+      s_next[s][tid] = nx;
+      k = min(k, nx);
+    }
+    int id = -1;
+    double b = INFINITY;
+    bool hit = false;
+    while (k < G.K) {                                 // k grows by at least 1 per pass: at most K passes
+      const double t = G.t0 + (double)k * G.step;
+      const double x[3] = {o[0] + t * d[0], o[1] + t * d[1], o[2] + t * d[2]};
+      double best = INFINITY;
+      int arg = -1, knext = G.K;
+      for (int s = 0; s < n; ++s) {
+        int nx = s_next[s][tid];
+        if (nx <= k) {                                // never an excluded shape: its entry is K
+          bool inside;
+          int cell[3];
+          double v = render_sample(V, P, s, x, &inside, cell);
+          ++count;
+          nx = k + 1;
+          const int* e = V.n[s];
+          const int64_t brick = ((int64_t)(cell[0] / kBrick) * ((e[1] - 2) / kBrick + 1) + cell[1] / kBrick) *
+                                    ((e[2] - 2) / kBrick + 1) + cell[2] / kBrick;
+          if (s == medium) {
+            v = inside ? -v : -INFINITY;
+            // all nodes < 0: every product of a weight in [0, 1] with a node is <= -0, so is their sum, and the negated
+            // sample is >= +0 -- `v < 0` is false for either zero
+            if (skip && inside && !(v < 0.0) && B.hi[s][brick] < 0.0) nx = render_next_brick(G, V, P, s, o, d, k, cell);
+          } else if (!inside) {
+            v = INFINITY;
+            if (skip) nx = render_next_outside(G, V, P, s, o, d, k + 1);
+          } else if (skip && !(v < 0.0)) {
+            if (B.lo[s][brick] > 0.0) nx = render_next_brick(G, V, P, s, o, d, k, cell);
+          }
+          s_next[s][tid] = nx;
+          if (v < best) {
+            best = v;
+            arg = s;
+          }
+        }
+        knext = min(knext, nx);
+      }
+      if (best < 0.0) {
+        hit = true;
+        b = best;
+        id = arg;
+        break;
+      }
+      k = knext;
+    }
+    steps[4 * p + slot] = hit ? k : -1;
+    shape_id[4 * p + slot] = hit ? id : -1;
+    if (slot == 3) {
+      if (hit) lit = false;
+      break;
+    }
+    if (!hit) {                                       // slots 0 and 2: the background stays behind
+      if (slot == 1) {
+        s_keep[1][tid] = (double)G.K * G.step;
+        own = true;
+      }
+      break;
+    }
+    // the secant needs the segment's true F(x_{k-1}): a skip may have passed over that sample
+    const double tk = G.t0 + (double)k * G.step;
+    double dep = tk;
+    if (k > 0) {
+      const double tp = G.t0 + (double)(k - 1) * G.step;
+      const double xp[3] = {o[0] + tp * d[0], o[1] + tp * d[1], o[2] + tp * d[2]};
+      double a = INFINITY;
+      for (int s = 0; s < n; ++s) {
+        if (!((mask >> s) & 1u)) continue;
+        bool inside;
+        int cell[3];
+        double v = render_sample(V, P, s, xp, &inside, cell);
+        if (s == medium) v = inside ? -v : -INFINITY;
+        else if (!inside) v = INFINITY;
+        if (v < a) a = v;
+      }
+      // leaving the medium's box is no crossing of a field: the hit stays at t_k
+      if (a < INFINITY && a > -INFINITY && !(id == medium && !(b > -INFINITY))) dep = (tk - G.step) + G.step * (a / (a - b));
+    }
+    const double xh[3] = {o[0] + dep * d[0], o[1] + dep * d[1], o[2] + dep * d[2]};
+    const double hh = 0.5 * V.h[id];
+    double g[3], nn[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      double xa[3] = {xh[0], xh[1], xh[2]}, xb[3] = {xh[0], xh[1], xh[2]};
+      xa[a] = xh[a] + hh;
+      xb[a] = xh[a] - hh;
+      bool inside;
+      int cell[3];
+      const double va = render_sample(V, P, id, xa, &inside, cell);
+      const double vb = render_sample(V, P, id, xb, &inside, cell);
+      g[a] = va - vb;
+    }
+    const double gl = sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
+    const bool ok = gl > 0.0 && gl < INFINITY;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) nn[a] = ok ? g[a] / gl : -d[a];
+
+    if ((slot == 0 && L.ior[id] > 0.0) || (slot == 1 && id == medium)) {   // an interface of the liquid: refract
+      if (slot == 0) liq = id;
+      else s_keep[1][tid] = dep;
+      const double eta = slot == 0 ? 1.0 / L.ior[liq] : L.ior[liq];
+      double dn = (d[0] * nn[0] + d[1] * nn[1]) + d[2] * nn[2];
+      if (dn > 0.0) {                                 // the normal faces the arriving ray
+        dn = -dn;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) nn[a] = -nn[a];
+      }
+      const double c = -dn;
+      if (slot == 0) {
+        const double q = (L.ior[liq] - 1.0) / (L.ior[liq] + 1.0), r0 = q * q, m1 = 1.0 - c, m2 = m1 * m1;
+        s_keep[0][tid] = r0 + (1.0 - r0) * ((m2 * m2) * m1);
+      }
+      const double kk = 1.0 - (eta * eta) * (1.0 - c * c);
+      if (kk < 0.0) {                                 // total internal reflection: the liquid's own colour
+        own = true;
+        break;
+      }
+      const double w = eta * c - sqrt(kk);
+      double tv[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) tv[a] = eta * d[a] + w * nn[a];
+      const double tl = sqrt((tv[0] * tv[0] + tv[1] * tv[1]) + tv[2] * tv[2]);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        o[a] = xh[a] - L.bias * nn[a];
+        d[a] = tv[a] / tl;
+      }
+      medium = slot == 0 ? id : -1;
+      K = slot == 0 ? L.K_inside : C.K;
+      slot += 1;
+      continue;
+    }
+    // the surface finally shaded: Lambert from the normal as k_render_march stores it, rounded to float32
+    if (slot == 1) s_keep[1][tid] = dep;
+    sid = id;
+    double l[3] = {L.light[0], L.light[1], L.light[2]};
+    if (!L.has_light) {                               // the headlight: -d of the camera's ray, taken again, not carried
+      double o0[3], d0[3];
+      render_ray(C, i, j, o0, d0);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) l[a] = -d0[a];
+    }
+    lam = fmax(0.0, ((double)(float)nn[0] * l[0] + (double)(float)nn[1] * l[1]) + (double)(float)nn[2] * l[2]);
+    if (!L.shadows) break;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      o[a] = xh[a] + L.bias * nn[a];
+      d[a] = l[a];
+    }
+    medium = -1;
+    mask = L.opaque;
+    K = L.K_shadow;
+    slot = 3;
+  }
+
+  const double R = s_keep[0][tid], len = s_keep[1][tid];
+  const double w = 0.25 + 0.75 * ((lit ? 1.0 : 0.0) * lam);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double behind = sid >= 0 ? L.albedo[sid][a] * w : own ? L.albedo[liq][a] : L.background[a];
+    color[3 * p + a] = liq >= 0 ? R * L.background[a] + ((1.0 - R) * exp(-(L.absorb[liq][a] * len))) * behind : behind;
+  }
+  length[p] = liq >= 0 ? len : 0.0;
+  if (evals) evals[p] = count;
+}
+
+// the box filter of s x s sub-pixel colours, summed in row-major order, and floor(255 c + 0.5)
+__global__ void __launch_bounds__(kRenderBlock)
+k_render_resolve(const double* __restrict__ color, int W, int H, int s, unsigned char* __restrict__ rgb) {
+  const int64_t p = (int64_t)blockIdx.x * kRenderBlock + threadIdx.x;
+  if (p >= (int64_t)W * H) return;
+  const int i = (int)(p / W), j = (int)(p % W);
+  double sum[3] = {0.0, 0.0, 0.0};
+  for (int a = 0; a < s; ++a)
+    for (int b = 0; b < s; ++b) {
+      const int64_t q = ((int64_t)(i * s + a) * ((int64_t)W * s) + (j * s + b)) * 3;
+      if (a == 0 && b == 0) {
+        sum[0] = color[q], sum[1] = color[q + 1], sum[2] = color[q + 2];
+      } else {
+        sum[0] = sum[0] + color[q], sum[1] = sum[1] + color[q + 1], sum[2] = sum[2] + color[q + 2];
+      }
+    }
+  const double area = (double)(s * s);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    double q = floor(255.0 * (sum[a] / area) + 0.5);
+    q = fmin(fmax(q, 0.0), 255.0);                    // fmax drops a NaN
+    rgb[3 * p + a] = (unsigned char)(int)q;
+  }
+}
+
 // wave minimum in every lane (the tree of wave_sum); all 64 lanes active, no NaN among the operands
 __device__ __forceinline__ double wave_min(double v) {
   v = fmin(v, dpp_f64<0xB1>(v));
@@ -282,7 +543,8 @@ __device__ __forceinline__ double wave_min(double v) {
 }
 
 __global__ void __launch_bounds__(kRenderBlock)
-k_render_bricks(const void* __restrict__ vol, int dt, int n0, int n1, int n2, int nb1, int nb2, double* __restrict__ out) {
+k_render_bricks(const void* __restrict__ vol, int dt, int n0, int n1, int n2, int nb1, int nb2, int maxima,
+                double* __restrict__ out) {
   __shared__ double s_part[kRenderBlock / kWave];
   const int tid = threadIdx.x;
   const int b2 = (int)(blockIdx.x % (unsigned)nb2), b1 = (int)((blockIdx.x / (unsigned)nb2) % (unsigned)nb1),
@@ -292,6 +554,7 @@ k_render_bricks(const void* __restrict__ vol, int dt, int n0, int n1, int n2, in
     const int i0 = kBrick * b0 + q / 81, i1 = kBrick * b1 + (q / 9) % 9, i2 = kBrick * b2 + q % 9;
     if (i0 < n0 && i1 < n1 && i2 < n2) {
       double v = ldx(vol, dt, ((int64_t)i0 * n1 + i1) * n2 + i2);
+      if (maxima) v = -v;                             // max = -min(-v), exactly
       if (v != v) v = -INFINITY;
       m = fmin(m, v);
     }
@@ -302,7 +565,7 @@ k_render_bricks(const void* __restrict__ vol, int dt, int n0, int n1, int n2, in
   if (tid == 0) {
 #pragma unroll
     for (int w = 1; w < kRenderBlock / kWave; ++w) m = fmin(m, s_part[w]);
-    out[blockIdx.x] = m;
+    out[blockIdx.x] = maxima ? -m : m;
   }
 }
 
@@ -382,7 +645,95 @@ int mfs_render_bricks3d(const void* volume, int dtype, const int64_t extents[3],
   const int nb1 = (int)((extents[1] - 2) / kBrick + 1), nb2 = (int)((extents[2] - 2) / kBrick + 1);
   const int64_t blocks = mfs_render_brick_count3d(extents);
   hipLaunchKernelGGL(k_render_bricks, dim3((unsigned)blocks), dim3(kRenderBlock), 0, (hipStream_t)stream, volume, dtype,
-                     (int)extents[0], (int)extents[1], (int)extents[2], nb1, nb2, (double*)bricks);
+                     (int)extents[0], (int)extents[1], (int)extents[2], nb1, nb2, 0, (double*)bricks);
+  MFS_LAUNCH_CHECK();
+  return MFS_OK;
+}
+
+int mfs_render_bricks_max3d(const void* volume, int dtype, const int64_t extents[3], void* bricks, mfs_stream stream) {
+  MFS_REQUIRE(volume && extents && bricks, "null volume / extents / bricks");
+  MFS_REQUIRE(dtype_ok(dtype), "dtype");
+  MFS_REQUIRE(volume_extents_ok(extents), "volume extents must be >= 2, fewer than 2^31 nodes");
+  const int nb1 = (int)((extents[1] - 2) / kBrick + 1), nb2 = (int)((extents[2] - 2) / kBrick + 1);
+  const int64_t blocks = mfs_render_brick_count3d(extents);
+  hipLaunchKernelGGL(k_render_bricks, dim3((unsigned)blocks), dim3(kRenderBlock), 0, (hipStream_t)stream, volume, dtype,
+                     (int)extents[0], (int)extents[1], (int)extents[2], nb1, nb2, 1, (double*)bricks);
+  MFS_LAUNCH_CHECK();
+  return MFS_OK;
+}
+
+int mfs_render_paths3d(const double* camera, int ortho, int64_t width, int64_t height, double near, double step,
+                       int64_t num_steps, int64_t num_shapes, const void* const* volumes_host, const int* dtypes_host,
+                       const int64_t* extents_host, const double* origins_host, const double* spacings_host,
+                       const double* poses_host, const void* const* bricks_host, const void* const* bricks_max_host,
+                       int skip, const double* materials_host, const double* light_host, const int* background_host,
+                       int shadows, double bias, int64_t shadow_steps, int64_t inside_steps, void* color, void* steps,
+                       void* shape_id, void* length, void* evals, mfs_stream stream) {
+  RenderCamera C;
+  if (int st = fill_render_camera(&C, camera, ortho, width, height, near, step, num_steps)) return st;
+  MFS_REQUIRE(num_shapes >= 1 && num_shapes <= kMaxVolumes, "1 to 16 shapes per scene");
+  MFS_REQUIRE(volumes_host && dtypes_host && extents_host && origins_host && spacings_host && poses_host,
+              "null shape description");
+  MFS_REQUIRE(!skip || (bricks_host && bricks_max_host), "null brick grids");
+  MFS_REQUIRE(materials_host && background_host, "null materials / background");
+  MFS_REQUIRE(color && steps && shape_id && length, "null output");
+  MFS_REQUIRE(shadow_steps >= 1 && shadow_steps <= 65536 && inside_steps >= 1 && inside_steps <= 65536,
+              "shadow and inside steps must be in 1 .. 65536");
+  MFS_REQUIRE(isfinite(bias) && bias >= 0, "bias must be finite and >= 0");
+  const int m = (int)num_shapes;
+  Volumes V;
+  Poses P;
+  if (int st = fill_volumes(&V, &P, m, volumes_host, dtypes_host, extents_host, origins_host, spacings_host, poses_host))
+    return st;
+  RenderBrickPtrs B;
+  RenderLook L;
+  memset(&B, 0, sizeof(B));
+  memset(&L, 0, sizeof(L));
+  for (int i = 0; i < m; ++i) {
+    const double* mat = materials_host + 8 * i;      // kind (0 opaque, 1 liquid), r g b in 0 .. 1, ior, absorb r g b
+    MFS_REQUIRE(mat[0] == 0.0 || mat[0] == 1.0, "material kind must be 0 (opaque) or 1 (liquid)");
+    const bool liquid = mat[0] == 1.0;
+    for (int k = 0; k < 3; ++k) {
+      MFS_REQUIRE(isfinite(mat[1 + k]), "albedo must be finite");
+      L.albedo[i][k] = mat[1 + k];
+      MFS_REQUIRE(!liquid || (isfinite(mat[5 + k]) && mat[5 + k] >= 0), "absorb must be finite and >= 0");
+      L.absorb[i][k] = liquid ? mat[5 + k] : 0.0;
+    }
+    MFS_REQUIRE(!liquid || (mat[4] > 1.0 && mat[4] <= 4.0), "ior must be in (1, 4]");
+    L.ior[i] = liquid ? mat[4] : 0.0;
+    if (!liquid) L.opaque |= 1u << i;
+    MFS_REQUIRE(!skip || (bricks_host[i] && (!liquid || bricks_max_host[i])), "null brick grid");
+    B.lo[i] = skip ? (const double*)bricks_host[i] : nullptr;
+    B.hi[i] = skip && liquid ? (const double*)bricks_max_host[i] : nullptr;
+  }
+  for (int k = 0; k < 3; ++k) {
+    MFS_REQUIRE(background_host[k] >= 0 && background_host[k] <= 255, "background must be in 0 .. 255");
+    L.background[k] = (double)background_host[k] / 255.0;
+    if (light_host) {
+      MFS_REQUIRE(isfinite(light_host[k]), "light must be finite");
+      L.light[k] = light_host[k];
+    }
+  }
+  L.has_light = light_host ? 1 : 0;
+  L.shadows = shadows ? 1 : 0;
+  L.bias = bias;
+  L.K_shadow = (int)shadow_steps;
+  L.K_inside = (int)inside_steps;
+  const dim3 grid((unsigned)((C.W + kRenderTile - 1) / kRenderTile), (unsigned)((C.H + kRenderTile - 1) / kRenderTile));
+  hipLaunchKernelGGL(k_render_paths, grid, dim3(kRenderBlock), 0, (hipStream_t)stream, C, V, P, B, L, m, skip ? 1 : 0,
+                     (double*)color, (int*)steps, (int*)shape_id, (double*)length, (int*)evals);
+  MFS_LAUNCH_CHECK();
+  return MFS_OK;
+}
+
+int mfs_render_resolve3d(const void* color, int64_t width, int64_t height, int samples, void* rgb, mfs_stream stream) {
+  MFS_REQUIRE(color && rgb, "null color / rgb");
+  MFS_REQUIRE(samples >= 1 && samples <= 4, "samples must be in 1 .. 4");
+  MFS_REQUIRE(width >= 1 && height >= 1 && width * samples <= 16384 && height * samples <= 16384,
+              "image extents times samples must be in 1 .. 16384");
+  const int64_t pixels = width * height;
+  hipLaunchKernelGGL(k_render_resolve, dim3((unsigned)((pixels + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0,
+                     (hipStream_t)stream, (const double*)color, (int)width, (int)height, samples, (unsigned char*)rgb);
   MFS_LAUNCH_CHECK();
   return MFS_OK;
 }

@@ -249,6 +249,11 @@ SIGNATURES = {
     "mfs_render_march3d": (_i, [_pd, _i, _i64, _i64, _d, _d, _i64, _i64, C.POINTER(_p), _pint, _pi64, _pd, _pd, _pd,
                                 C.POINTER(_p), _i, _p, _p, _p, _p, _p, _p]),
     "mfs_render_shade3d": (_i, [_pd, _i, _i64, _i64, _p, _p, _i64, _pd, _pint, _pd, _p, _p]),
+    "mfs_render_bricks_max3d": (_i, [_p, _i, _pi64, _p, _p]),
+    "mfs_render_paths3d": (_i, [_pd, _i, _i64, _i64, _d, _d, _i64, _i64, C.POINTER(_p), _pint, _pi64, _pd, _pd, _pd,
+                                C.POINTER(_p), C.POINTER(_p), _i, _pd, _pd, _pint, _i, _d, _i64, _i64, _p, _p, _p, _p, _p,
+                                _p]),
+    "mfs_render_resolve3d": (_i, [_p, _i64, _i64, _i, _p, _p]),
 }
 
 _lib = None

@@ -8,8 +8,15 @@ over the shapes is negative, refines it by one secant step and takes the hit sha
 normal, shape id and step index.  `shade` turns that into Lambert bytes.  The bricks only save work: with skip=False the
 marcher visits every sample of every shape and returns the same bits.  tests/render_numpy.py restates the contract.
 
+`scene.trace(camera, look)` follows each ray further, under a `Look` of one `Material` per shape: an opaque surface is
+shadowed by the opaque shapes between it and the light; a liquid refracts the ray in and out once, absorbs along the path
+inside, and weighs what lies behind it by Fresnel's term; `look.samples`^2 rays per pixel.  It returns a `PathResult`
+(float colour, step and shape id per slot of the path, length inside the liquid) and `resolve` turns that into bytes.
+Opaque materials without shadows give `shade(render(...))` byte for byte.  tests/render_paths_numpy.py restates it.
+
     cam = render.Camera(eye=(0.9, 0.8, 1.1), target=(0, 0.3, 0), width=1920, height=1080)
     rgb = sim.render(cam)                                   # NotebookSimulation: the skin and the solid level set
+    rgb = sim.render(cam, look="water")                     # the skin as water over shadowed solids, 2 x 2 rays per pixel
     render.save_png("frame.png", rgb)
 """
 from __future__ import annotations
@@ -177,12 +184,17 @@ class Scene:
         self.shapes = _shapes(shapes)
         self.device = self.shapes[0].volume.phi.device
         self.bricks = []
+        self.bricks_max = [None] * len(self.shapes)      # brick maxima: of the shapes a `trace` has seen as a liquid
         self.refresh()
 
     def refresh(self):
-        """rebuild every shape's brick minima from its volume as it is now"""
+        """rebuild every shape's brick minima (and the maxima that were built) from its volume as it is now"""
         lib = _lib.load()
         self.bricks = []
+        built = [k for k, g in enumerate(self.bricks_max) if g is not None]
+        self.bricks_max = [None] * len(self.shapes)
+        for k in built:
+            self._maxima(k)
         with torch.cuda.device(self.device):
             for s in self.shapes:
                 phi = s.volume.phi
@@ -217,6 +229,182 @@ class Scene:
                 stats.update(pixels=W * H, hits=int((steps >= 0).sum().item()),
                              samples=int(evals.sum(dtype=torch.int64).item()), num_steps=K)
         return RenderResult(depth, normal, ident, steps, near, far, step, K, m)
+
+    def _maxima(self, k):
+        """shape k's grid of brick maxima, built at its first use as a liquid and kept up by `refresh()`"""
+        if self.bricks_max[k] is None:
+            lib = _lib.load()
+            phi = self.shapes[k].volume.phi
+            with torch.cuda.device(self.device):
+                grid = torch.empty(tuple((int(n) - 2) // BRICK + 1 for n in phi.shape), dtype=torch.float64, device=self.device)
+                _lib.check(lib.mfs_render_bricks_max3d(T.ptr(phi), T.code(phi), _lib.i64x(phi.shape), T.ptr(grid), T.stream()),
+                           "mfs_render_bricks_max3d")
+            self.bricks_max[k] = grid
+        return self.bricks_max[k]
+
+    def trace(self, camera, look, step=None, skip=True, stats=None):
+        """The path of every sub-pixel ray of `camera` under `look` (a `Look`): shadows, one refraction through a liquid,
+        `look.samples`^2 rays per pixel -- a `PathResult`; `resolve` turns it into bytes.  step, skip, stats: as `render`
+        (`hits` counts the rays whose first march hit).  tests/render_paths_numpy.py restates every operation."""
+        near, far, step, K, bias, Ks, Ki = plan_paths(self.shapes, camera, look, step)
+        s = look.samples
+        W, H = s * camera.width, s * camera.height
+        lib = _lib.load()
+        m, dev = len(self.shapes), self.device
+        grids = (ctypes.c_void_p * m)(*[g.data_ptr() for g in self.bricks])
+        tops = (ctypes.c_void_p * m)(*[self._maxima(k).data_ptr() if mat.is_liquid else None
+                                       for k, mat in enumerate(look.materials)])
+        with torch.cuda.device(dev):
+            color = torch.empty((H, W, 3), dtype=torch.float64, device=dev)
+            steps = torch.empty((H, W, 4), dtype=torch.int32, device=dev)
+            ident = torch.empty((H, W, 4), dtype=torch.int32, device=dev)
+            length = torch.empty((H, W), dtype=torch.float64, device=dev)
+            evals = torch.empty((H, W), dtype=torch.int32, device=dev) if stats is not None else None
+            _lib.check(lib.mfs_render_paths3d(_lib.f64x(camera.packed()), int(camera.ortho), W, H, near, step, K, m,
+                                              *_volumes.pack_shapes(self.shapes), grids, tops, int(bool(skip)),
+                                              _lib.f64x(look.packed()), None if look.light is None else _lib.f64x(look.light),
+                                              (ctypes.c_int * 3)(*look.background), int(look.shadows), bias, Ks, Ki,
+                                              T.ptr(color), T.ptr(steps), T.ptr(ident), T.ptr(length),
+                                              None if evals is None else T.ptr(evals), T.stream()),
+                       "mfs_render_paths3d")
+            if stats is not None:
+                stats.update(pixels=W * H, hits=int((steps[..., 0] >= 0).sum().item()),
+                             samples=int(evals.sum(dtype=torch.int64).item()), num_steps=K)
+        return PathResult(color, steps, ident, length, near, far, step, K, m, s, bias, Ks, Ki)
+
+
+class Material:
+    """What a shape is made of: `Material.opaque(color)` or `Material.liquid(color, ior, absorb)`; color (r, g, b) in
+    0 .. 255, ior in (1, 4], absorb (r, g, b) >= 0 per world unit (Beer-Lambert along the path inside the liquid)."""
+
+    def __init__(self, color, ior=None, absorb=(0.0, 0.0, 0.0)):
+        self.color = tuple(T.as_f64_list(color, 3))
+        if not all(0.0 <= v <= 255.0 for v in self.color):
+            raise ValueError(f"material: colour components must be in 0 .. 255, got {self.color}")
+        self.ior = None if ior is None else float(ior)
+        self.absorb = tuple(T.as_f64_list(absorb, 3))
+        if self.ior is not None:
+            if not (1.0 < self.ior <= 4.0):
+                raise ValueError(f"material: ior must be in (1, 4], got {self.ior}")
+            if not all(math.isfinite(v) and v >= 0.0 for v in self.absorb):
+                raise ValueError(f"material: absorb must be finite and >= 0, got {self.absorb}")
+
+    @classmethod
+    def opaque(cls, color):
+        return cls(color)
+
+    @classmethod
+    def liquid(cls, color, ior=1.33, absorb=(3.0, 1.2, 0.4)):
+        return cls(color, ior, absorb)
+
+    @property
+    def is_liquid(self):
+        return self.ior is not None
+
+    def packed(self):
+        return [float(self.is_liquid)] + [v / 255.0 for v in self.color] + [self.ior or 0.0] + list(self.absorb)
+
+
+class Look:
+    """How `Scene.trace` shades: one `Material` per shape; light: a vector towards a directional light, None: a headlight
+    (l = -d of the camera's ray); background (r, g, b) in 0 .. 255; shadows: opaque shapes shadow the surface finally
+    shaded (a liquid casts none); samples: s x s rays per pixel on the regular grid, 1 .. 4; bias: how far off a surface a
+    secondary ray starts, default 4 steps; shadow_steps / inside_steps: samples of the shadow march and of the march
+    inside the liquid, default the camera ray's.  Everything is checked here, without a device."""
+
+    def __init__(self, materials, light, background=(255, 255, 255), shadows=True, samples=1, bias=None, shadow_steps=None,
+                 inside_steps=None):
+        self.materials = list(materials)
+        if not (1 <= len(self.materials) <= MAX_SHAPES) or not all(isinstance(q, Material) for q in self.materials):
+            raise ValueError(f"look: expected 1 .. {MAX_SHAPES} mfs.render.Material, one per shape")
+        self.light = None
+        if light is not None:
+            light = np.asarray(T.as_f64_list(light, 3), np.float64)
+            if not (np.isfinite(light).all() and float(np.abs(light).max()) > 0):
+                raise ValueError("look: light must be a finite, non-zero vector towards the light")
+            self.light = _unit(light)
+        self.background = [int(v) for v in background]
+        if len(self.background) != 3 or not all(0 <= v <= 255 for v in self.background):
+            raise ValueError(f"look: background must be (r, g, b) in 0 .. 255, got {tuple(background)}")
+        self.shadows = bool(shadows)
+        self.samples = int(samples)
+        if not (1 <= self.samples <= 4) or self.samples != samples:
+            raise ValueError(f"look: samples must be an integer in 1 .. 4, got {samples}")
+        self.bias = None if bias is None else float(bias)
+        if self.bias is not None and not (math.isfinite(self.bias) and self.bias >= 0.0):
+            raise ValueError(f"look: bias must be finite and >= 0, got {bias}")
+        self.shadow_steps = None if shadow_steps is None else int(shadow_steps)
+        self.inside_steps = None if inside_steps is None else int(inside_steps)
+        for name, v in (("shadow_steps", self.shadow_steps), ("inside_steps", self.inside_steps)):
+            if v is not None and not (1 <= v <= MAX_STEPS):
+                raise ValueError(f"look: {name} must be in 1 .. {MAX_STEPS}, got {v}")
+
+    def packed(self):
+        return [v for q in self.materials for v in q.packed()]
+
+    @classmethod
+    def water(cls, count=2, liquid=0, **kw):
+        """the default of `NotebookSimulation.render(look="water")`: shape `liquid` of `count` is water (ior 1.33, absorbing
+        red most), the others an opaque warm grey; a light from above, shadows on, 2 x 2 rays per pixel"""
+        mats = [Material.liquid(LIQUID_COLOR) if k == liquid else Material.opaque(SOLID_COLOR) for k in range(count)]
+        return cls(mats, **{**dict(light=(0.3, 2.0, 0.4), samples=2), **kw})
+
+
+class PathResult(NamedTuple):
+    """color (sH, sW, 3) float64, the colour of every sub-pixel ray; steps and shape_id (sH, sW, 4) int32 per slot of the
+    path (0 the camera's ray, 1 inside the liquid, 2 after the exit, 3 the shadow ray): the hit sample and shape, -1 at a
+    miss, -2 where the slot was not run; length (sH, sW) float64, the path's length inside the liquid, 0 without one;
+    near / far / step / num_steps / num_shapes as `RenderResult`; samples, bias, shadow_steps, inside_steps as run."""
+    color: torch.Tensor
+    steps: torch.Tensor
+    shape_id: torch.Tensor
+    length: torch.Tensor
+    near: float
+    far: float
+    step: float
+    num_steps: int
+    num_shapes: int
+    samples: int
+    bias: float
+    shadow_steps: int
+    inside_steps: int
+
+
+def plan_paths(shapes, camera, look, step=None):
+    """(near, far, step, num_steps, bias, shadow_steps, inside_steps) of `Scene.trace`, after every refusal that needs no
+    device: `plan`'s, one material per shape, the supersampled extents within 1 .. 16384"""
+    near, far, step, K = plan(shapes, camera, step)
+    if not isinstance(look, Look):
+        raise TypeError(f"look: expected an mfs.render.Look, got {type(look).__name__}")
+    if len(look.materials) != len(shapes):
+        raise ValueError(f"look: {len(look.materials)} materials for {len(shapes)} shapes: expected one per shape")
+    check_sizes(look.samples * camera.width, look.samples * camera.height, K)
+    bias = 4.0 * step if look.bias is None else look.bias
+    return near, far, step, K, bias, look.shadow_steps or K, look.inside_steps or K
+
+
+def resolve(result):
+    """(H, W, 3) uint8 on the result's device: the samples^2 colours of each pixel summed in row-major order, divided by
+    samples^2, rounded floor(255 c + 0.5)"""
+    if not isinstance(result, PathResult):
+        raise TypeError(f"result: expected a PathResult, got {type(result).__name__}")
+    if not result.color.is_cuda:
+        raise TypeError(f"result is on {result.color.device}; resolving runs on the GPU only (no CPU fallback)")
+    s = result.samples
+    H, W = int(result.color.shape[0]) // s, int(result.color.shape[1]) // s
+    lib = _lib.load()
+    dev = result.color.device
+    with torch.cuda.device(dev):
+        rgb = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+        _lib.check(lib.mfs_render_resolve3d(T.ptr(result.color), W, H, s, T.ptr(rgb), T.stream()), "mfs_render_resolve3d")
+    return rgb
+
+
+def image_paths(shapes, camera, look, step=None, skip=True):
+    """`resolve(Scene(shapes).trace(camera, look, step, skip))`: (H, W, 3) uint8"""
+    listed = _shapes(shapes, device=False)                                # everything a host can refuse, first
+    plan_paths(listed, camera, look, step)
+    return resolve(Scene(listed).trace(camera, look, step, skip))
 
 
 def _palette(colors, count):
@@ -322,3 +510,25 @@ def simulation_image(sim, camera, what=("liquid", "solid"), colors=None, step=No
     if colors is None:
         colors = [LIQUID_COLOR if w == "liquid" else SOLID_COLOR for w in names]
     return image(shapes, camera, colors, step=step)
+
+
+def simulation_look(what, look):
+    """`look` of `NotebookSimulation.render` as a `Look` for the shapes named by `what`: "water" -> `Look.water` with the
+    skin as the liquid"""
+    names = (what,) if isinstance(what, str) else tuple(what)
+    if isinstance(look, str):
+        if look != "water":
+            raise ValueError(f'look: expected an mfs.render.Look or "water", got {look!r}')
+        return Look.water(len(names), names.index("liquid") if "liquid" in names else -1)
+    if not isinstance(look, Look):
+        raise TypeError(f'look: expected an mfs.render.Look or "water", got {type(look).__name__}')
+    return look
+
+
+def simulation_paths(sim, camera, what, look, step=None, trace=False):
+    """the image of `NotebookSimulation.render(look=...)`; trace=True: (the `PathResult`, the `Look`) instead"""
+    look = simulation_look(what, look)
+    shapes = simulation_shapes(sim, what)[1]
+    if trace:
+        return Scene(shapes).trace(camera, look, step), look
+    return image_paths(shapes, camera, look, step)

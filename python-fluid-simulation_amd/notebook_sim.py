@@ -172,10 +172,16 @@ class NotebookSimulation:
         `solid_levelset.phi` (the analytic and the mesh bodies united); shape ids count in the order of `what`."""
         return _render.simulation_result(self, camera, what, step)
 
-    def render(self, camera, what=("liquid", "solid"), colors=None, step=None):
+    def render(self, camera, what=("liquid", "solid"), colors=None, step=None, look=None):
         """`render_result` shaded: an (H, W, 3) uint8 image on the GPU, white where a ray meets nothing;
-        `mfs.render.save_png` writes it.  colors: one (r, g, b) in 0 .. 255 per entry of `what`."""
-        return _render.simulation_image(self, camera, what, colors, step)
+        `mfs.render.save_png` writes it.  colors: one (r, g, b) in 0 .. 255 per entry of `what`.
+        look: None: headlight Lambert on opaque surfaces, as above.  An `mfs.render.Look` with one material per entry of
+        `what` (the skin takes the liquid one), or "water" (`mfs.render.Look.water`: the skin refracts at ior 1.33 and
+        absorbs, the solids are opaque and cast shadows, a light from above, 2 x 2 rays per pixel): the paths of
+        `mfs.render.Scene.trace`, resolved; `colors` then plays no part."""
+        if look is None:
+            return _render.simulation_image(self, camera, what, colors, step)
+        return _render.simulation_paths(self, camera, what, look, step)
 
     def step(self, duration_left=float("inf"), timings=None):
         """One pass of the loop body (ipynb:4571-4667, solver == 'apic').  Returns the dt it took."""
@@ -303,7 +309,7 @@ class SlabNotebookSimulation(NotebookSimulation):
         raise NotImplementedError("render() is single-GPU: gather the particles and the level set to one rank and call "
                                   "mfs.render.image")
 
-    def render(self, camera, what=("liquid", "solid"), colors=None, step=None):
+    def render(self, camera, what=("liquid", "solid"), colors=None, step=None, look=None):
         return self.render_result(camera, what, step)
 
     def close(self):
