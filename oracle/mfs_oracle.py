@@ -111,9 +111,12 @@ def _theta(phi, nphi):
         return np.minimum(1.0, np.maximum(0.01, phi / (phi - nphi)))
 
 
-def pressure_rhs3d(cell_size, gres, vx, vy, vz, sphi, sv, lphi, b, wx, wy, wz):
-    """solver/PressureCGSolver3D.py:6-50 (initialize_solver_kernel)."""
+def pressure_rhs3d(cell_size, gres, vx, vy, vz, sphi, sv, lphi, b, wx, wy, wz, mag=None):
+    """solver/PressureCGSolver3D.py:6-50 (initialize_solver_kernel).  `mag`, if a dict, receives under "b" a cell array
+    holding, on the interior cells, the sum of the absolute values of the terms that the kernel adds (0 elsewhere)."""
     Nx, Ny, Nz = (int(g) for g in gres)
+    if mag is not None:
+        mag["b"] = np.zeros((Nx, Ny, Nz))
     if min(Nx, Ny, Nz) < 3:
         return                       # no interior cell: the kernel's every thread returns at :8-10
     cs = [float(c) for c in cell_size]
@@ -138,14 +141,19 @@ def pressure_rhs3d(cell_size, gres, vx, vy, vz, sphi, sv, lphi, b, wx, wy, wz):
     for w, v, sgn, c, s in terms:
         bv = bv + sgn * (w * v / c)
         bv = bv - sgn * np.where(w < 1, w * s / c, 0.0)
+        if mag is not None:
+            mag["b"][I] += np.abs(w * v / c) + np.where(w < 1, np.abs(w * s / c), 0.0)
     fluid = np.asarray(lphi, F64)[I] < 0
     b[I] = np.where(fluid, bv, 0.0)
 
 
-def pressure_apply3d(gres, v, out, wx, wy, wz, lphi):
+def pressure_apply3d(gres, v, out, wx, wy, wz, lphi, mag=None):
     """solver/PressureCGSolver3D.py:52-130 (matvecmul_kernel).  Boundary cells of
-    `out` are not written (:55-57); non-fluid interior cells get 0 (:60-63)."""
+    `out` are not written (:55-57); non-fluid interior cells get 0 (:60-63).  `mag`, if a dict, receives under "out" a
+    cell array holding, on the interior cells, |diag| |v| + the sum of |w v| over the fluid neighbours (0 elsewhere)."""
     Nx, Ny, Nz = (int(g) for g in gres)
+    if mag is not None:
+        mag["out"] = np.zeros((Nx, Ny, Nz))
     if min(Nx, Ny, Nz) < 3:
         return
     I = (slice(1, Nx - 1), slice(1, Ny - 1), slice(1, Nz - 1))
@@ -166,13 +174,18 @@ def pressure_apply3d(gres, v, out, wx, wy, wz, lphi):
         nf = nphi < 0
         val = val - np.where(nf, w * sh(v, *off), 0.0)
         diag = diag + np.where(nf, w, w / _theta(phi, nphi))
+        if mag is not None:
+            mag["out"][I] += np.where(nf, np.abs(w * sh(v, *off)), 0.0)
     val = val + diag * sh(v, 0, 0, 0)
+    if mag is not None:
+        mag["out"][I] = np.where(phi < 0, mag["out"][I] + np.abs(diag * sh(v, 0, 0, 0)), 0.0)
     out[I] = np.where(phi < 0, val, 0.0)
 
 
-def pressure_update3d(gres, cell_size, vx, vy, vz, pv, wx, wy, wz, sv, lphi):
+def pressure_update3d(gres, cell_size, vx, vy, vz, pv, wx, wy, wz, sv, lphi, mag=None):
     """solver/PressureCGSolver3D.py:132-153 (apply_pressure_kernel): x,y,z in
-    [1, N-1]; in-place, result cast to the velocity dtype (Q11)."""
+    [1, N-1]; in-place, result cast to the velocity dtype (Q11).  `mag`, if a dict, receives under each axis a face array
+    holding, on the faces with x, y, z >= 1, |w| (|v| + (|p| + |p neighbour|) c / theta) + |1 - w| |sv| (0 elsewhere)."""
     Nx, Ny, Nz = (int(g) for g in gres)
     cs = [float(c) for c in cell_size]
     lphi = np.asarray(lphi, F64)
@@ -193,6 +206,10 @@ def pressure_update3d(gres, cell_size, vx, vy, vz, pv, wx, wy, wz, sv, lphi):
         old = np.asarray(vel)[C].astype(F64)
         new = old + (pv[C] - pv[M]) * c / theta
         new = wv * new + (1 - wv) * svs
+        if mag is not None:
+            mag[axis] = np.zeros(np.shape(vel))
+            mag[axis][C] = (np.abs(wv) * (np.abs(old) + (np.abs(pv[C]) + np.abs(pv[M])) * c / theta)
+                            + np.abs(1 - wv) * np.abs(svs))
         vel[C] = np.where(act, new, old).astype(vel.dtype)
 
 
@@ -753,9 +770,12 @@ def _nonsolid_frac(gres, wx, wy, wz):
     return (a(wx, 0, 0, 0) + a(wx, 1, 0, 0) + a(wy, 0, 0, 0) + a(wy, 0, 1, 0) + a(wz, 0, 0, 0) + a(wz, 0, 0, 1)) / 6
 
 
-def density_fix_volume3d(cell_size, gres, lvol, gvol, sphi, lphi, wx, wy, wz):
-    """fix_volume_kernel :38-86 (`lvol` is unused there, as in the reference)."""
+def density_fix_volume3d(cell_size, gres, lvol, gvol, sphi, lphi, wx, wy, wz, mag=None):
+    """fix_volume_kernel :38-86 (`lvol` is unused there, as in the reference).  `mag`, if a dict, receives under "gvol" a
+    cell array holding, on the interior cells, cell volume * (sum of the six |w|) / 6 (0 elsewhere)."""
     Nx, Ny, Nz = (int(g) for g in gres)
+    if mag is not None:
+        mag["gvol"] = np.zeros((Nx, Ny, Nz))
     if min(Nx, Ny, Nz) < 3:
         return
     cs = np.asarray(cell_size, F64)
@@ -768,12 +788,20 @@ def density_fix_volume3d(cell_size, gres, lvol, gvol, sphi, lphi, wx, wy, wz):
     for off in ((1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)):
         internal = internal & (sh(lphi, *off) < 0)
     fluid_vol = np.where(internal & ~near_solid, cvol, fluid_vol)
+    if mag is not None:
+        mag["gvol"][I] = cvol * _nonsolid_frac(gres, np.abs(wx), np.abs(wy), np.abs(wz))
     gvol[I] = np.minimum(fluid_vol, cvol * _nonsolid_frac(gres, wx, wy, wz))
 
 
-def density_rhs3d(rho0, dt, gres, cell_size, gm, gvol, lphi, wx, wy, wz, b):
-    """initialize_solver_kernel :88-116."""
+def density_rhs3d(rho0, dt, gres, cell_size, gm, gvol, lphi, wx, wy, wz, b, mag=None):
+    """initialize_solver_kernel :88-116.  `mag`, if a dict, receives under "b" a cell array holding, on the interior cells,
+    the magnitude that the rounding errors of b scale with: the terms of every sum in absolute value, carried through the
+    quotients,  (frac (A_mass / |cell_mass| + A_vol / |cell_vol| + 1) + 1 + |frac|) / dt  with
+    A_solid = (1 + nonsolid fraction) cell volume, A_mass = |gm| + rho0 A_solid, A_vol = |gvol| + A_solid and frac the
+    density fraction before its clamp (0 outside the interior and where cell_mass < 1e-10, where b is exactly 0)."""
     Nx, Ny, Nz = (int(g) for g in gres)
+    if mag is not None:
+        mag["b"] = np.zeros((Nx, Ny, Nz))
     if min(Nx, Ny, Nz) < 3:
         return
     cvol = float(np.prod(np.asarray(cell_size, F64)))
@@ -783,15 +811,23 @@ def density_rhs3d(rho0, dt, gres, cell_size, gm, gvol, lphi, wx, wy, wz, b):
     cell_mass = np.asarray(gm, F64)[I] + solid_mass
     cell_vol = np.asarray(gvol, F64)[I] + solid_vol
     frac = cell_mass / np.maximum(cell_vol, 1e-10) / rho0
+    if mag is not None:
+        a_solid = (1 + _nonsolid_frac(gres, np.abs(wx), np.abs(wy), np.abs(wz))) * cvol
+        with np.errstate(divide="ignore", invalid="ignore"):
+            amp = ((np.abs(np.asarray(gm, F64)[I]) + rho0 * a_solid) / np.abs(cell_mass)
+                   + np.where(cell_vol > 1e-10, (np.abs(np.asarray(gvol, F64)[I]) + a_solid) / np.abs(cell_vol), 0.0) + 1)
+            mag["b"][I] = np.where(cell_mass < 1e-10, 0.0, (np.abs(frac) * amp + 1 + np.abs(frac)) / dt)
     frac = np.where(cell_mass < 1e-10, 1.0, frac)
     frac = np.maximum(0.5, np.minimum(1.5, frac))
     b[I] = np.where(np.asarray(lphi, F64)[I] >= 0, 0.0, (1 - frac) / dt)
 
 
-def density_apply3d(gres, v, out, wx, wy, wz, lphi):
+def density_apply3d(gres, v, out, wx, wy, wz, lphi, mag=None):
     """matvecmul_kernel :118-207: diag counts 1 per fluid neighbour (1/theta per non-fluid one), and the
-    -z tap is weighted by wz[x,y,z+1] (:184, kept as written)."""
+    -z tap is weighted by wz[x,y,z+1] (:184, kept as written).  `mag`: as in pressure_apply3d."""
     Nx, Ny, Nz = (int(g) for g in gres)
+    if mag is not None:
+        mag["out"] = np.zeros((Nx, Ny, Nz))
     if min(Nx, Ny, Nz) < 3:
         return
     I = (slice(1, Nx - 1), slice(1, Ny - 1), slice(1, Nz - 1))
@@ -807,12 +843,17 @@ def density_apply3d(gres, v, out, wx, wy, wz, lphi):
         nf = nphi < 0
         val = val - np.where(nf, w * sh(v, *off), 0.0)
         diag = diag + np.where(nf, 1.0, 1.0 / _theta(phi, nphi))
+        if mag is not None:
+            mag["out"][I] += np.where(nf, np.abs(w * sh(v, *off)), 0.0)
     val = val + diag * sh(v, 0, 0, 0)
+    if mag is not None:
+        mag["out"][I] = np.where(phi < 0, mag["out"][I] + np.abs(diag * sh(v, 0, 0, 0)), 0.0)
     out[I] = np.where(phi < 0, val, 0.0)
 
 
-def density_displacement3d(gres, dt, cell_size, dx, dy, dz, pv, lphi):
-    """compute_displacement_kernel :209-222 (x,y,z in [1, N-1])."""
+def density_displacement3d(gres, dt, cell_size, dx, dy, dz, pv, lphi, mag=None):
+    """compute_displacement_kernel :209-222 (x,y,z in [1, N-1]).  `mag`, if a dict, receives under each axis a face array
+    holding, on the faces with x, y, z >= 1, (|p| + |p neighbour|) dt c / theta (0 elsewhere)."""
     Nx, Ny, Nz = (int(g) for g in gres)
     cs = np.asarray(cell_size, F64)
     P, L = np.asarray(pv, F64), np.asarray(lphi, F64)
@@ -821,6 +862,9 @@ def density_displacement3d(gres, dt, cell_size, dx, dy, dz, pv, lphi):
         m = tuple(slice(0, n - 1) if a == ax else slice(1, n) for a, n in enumerate((Nx, Ny, Nz)))
         th = np.minimum(1.0, np.maximum(0.01, edge_in_fraction(L[c], L[m])))
         out[c] = (P[c] - P[m]) * dt * cs[ax] / th
+        if mag is not None:
+            mag[ax] = np.zeros(np.shape(out))
+            mag[ax][c] = (np.abs(P[c]) + np.abs(P[m])) * dt * cs[ax] / th
 
 
 def density_advect3d(px, d, bound_min, cell_size, grid_bias, axis):
