@@ -928,6 +928,47 @@ int mfs_render_paths3d(const double* camera, int ortho, int64_t width, int64_t h
                        void* shape_id, void* length, void* evals, mfs_stream stream);
 int mfs_render_resolve3d(const void* color, int64_t width, int64_t height, int samples, void* rgb, mfs_stream stream);
 
+/* ------------------------------------------------------------------------- */
+/* Particle data at points (csrc/mfs_attrib.hip; DESIGN.md "Particle data at points") */
+/* ------------------------------------------------------------------------- */
+/* No reference counterpart.  Additions: the ABI version stays.
+ * Particles x_i (P x 3, float32 / float64) carry values a_i (P x C, C in 1 .. 4, float32 / float64, rounded to float32
+ * on load); queries y_q (Q x 3, float32 / float64); an influence radius R > 0.  With d = x_i - y_q, t = 1 - |d|^2 / R^2
+ * and w_qi = t^3 where t > 0, otherwise 0 (strict: a particle exactly R away adds nothing), W_q = sum_i w_qi and
+ * A_q = sum_i w_qi a_i / W_q where W_q > 0; where W_q == 0 every channel is `fill`.  A particle whose position is not
+ * finite adds nothing, a non-finite value of a contributing particle propagates, a query that is not finite is
+ * uncovered (weight 0, values fill).  fp32 arithmetic on coordinates taken relative to the query's bin in fp64 first.
+ * Bins: a lattice of shape (m0, m1, m2) cubic bins of edge exactly R with float64 origin o; the bin of a position is
+ * c_a = floor((x_a - o_a) / R) in float64, its key (c0 m1 + c1) m2 + c2, and m0 m1 m2 (the sentinel) for a position
+ * outside the lattice or not finite.  At most 2^31 - 2 bins.  A query in bin c takes contributions from the 27 bins
+ * around c and from nothing else (a particle within R whose own bin index rounds one bin further away is lost: its
+ * weight is below 1e-15).  A query with the sentinel key is not touched: the caller stores fill and weight 0.
+ * _bins3d: m0 m1 m2, or 0 when an extent is < 1 or the product exceeds 2^31 - 2.
+ * _keys3d: keys (DEVICE, count int32) of `positions`; box_host: null, or 6 HOST doubles lo[3], hi[3]: a position outside
+ * the closed box gets the sentinel as well.
+ * _gather3d: sorted_particles / sorted_values: the particles and their values in a STABLE sort by key (the caller's
+ * order inside a bin is the order of summation: the result is a function of the input alone; no atomics);
+ * bin_starts: bins + 1 int32, the index of the first sorted particle with key >= b.  sorted_queries: the queries in a
+ * stable sort by key, query_rows (int64) the row of `values` / `weight` each came from.  items: num_items x 3 int32
+ * (key, first, count): the sorted queries first .. first + count - 1, count <= 256, all of bin `key`; one workgroup
+ * each.  values: DEVICE num_queries x channels float32; weight: num_queries float32; tested: null, or num_items int32,
+ * the particles each item's lanes looped over.
+ * _shade_albedo3d: _shade3d with one change: a pixel with shape_id == albedo_id takes pixel_albedo (DEVICE, height x
+ * width x 3 float32, in 0 .. 1) in place of albedo_host[albedo_id]; where a component of it is NaN the pixel keeps the
+ * palette's colour.                                                                                                */
+int64_t mfs_attrib_bins3d(const int64_t shape[3]);
+int mfs_attrib_keys3d(const int64_t shape[3], const double origin[3], double influence, const double* box_host,
+                      const void* positions, int p_dt, int64_t count, void* keys, mfs_stream stream);
+int mfs_attrib_gather3d(const int64_t shape[3], const double origin[3], double influence, int channels, double fill,
+                        const void* sorted_particles, int p_dt, const void* sorted_values, int v_dt, int64_t num_particles,
+                        const void* bin_starts, const void* sorted_queries, int q_dt, const void* query_rows,
+                        int64_t num_queries, const void* items, int64_t num_items, void* values, void* weight, void* tested,
+                        mfs_stream stream);
+int mfs_render_shade_albedo3d(const double* camera, int ortho, int64_t width, int64_t height, const void* normal,
+                              const void* shape_id, int64_t num_colors, const double* albedo_host,
+                              const int* background_host, const double* light_host, const void* pixel_albedo,
+                              int64_t albedo_id, void* rgb, mfs_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@
 //   k_render_march   one lane per pixel, one wave per 8 x 8 pixel tile: walks the samples t_k = near + k * step of its ray,
 //                    stops at the first with min over the shapes < 0, refines by one secant step, takes the normal
 //   k_render_shade   Lambert from the normals and shape ids, one lane per pixel
+//   k_render_shade_albedo  the same with a per-pixel albedo for one shape (the liquid coloured by particle data)
 //   k_render_paths   one lane per sub-pixel ray: up to four such marches in a loop over the path's state -- the camera's
 //                    ray, inside a refracting liquid, after the exit, the shadow ray -- and the path's colour
 //   k_render_resolve the box filter of the sub-pixel colours and the byte conversion
@@ -600,6 +601,47 @@ k_render_shade(RenderCamera C, RenderPalette P, const float* __restrict__ normal
   }
 }
 
+// k_render_shade with one change: a pixel of shape albedo_id takes its albedo from pixel_albedo (H x W x 3 float32) in
+// place of the palette's; a pixel whose albedo has a NaN component keeps the palette's
+__global__ void __launch_bounds__(kRenderBlock)
+k_render_shade_albedo(RenderCamera C, RenderPalette P, const float* __restrict__ normal, const int* __restrict__ shape_id,
+                      const float* __restrict__ pixel_albedo, int albedo_id, unsigned char* __restrict__ rgb) {
+  const int64_t p = (int64_t)blockIdx.x * kRenderBlock + threadIdx.x;
+  if (p >= (int64_t)C.W * C.H) return;
+  const int id = shape_id[p];
+  if (id < 0 || id >= P.n) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) rgb[3 * p + a] = (unsigned char)P.background[a];
+    return;
+  }
+  double l[3] = {P.light[0], P.light[1], P.light[2]};
+  if (!P.has_light) {
+    double o[3], d[3];
+    render_ray(C, (int)(p / C.W), (int)(p % C.W), o, d);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) l[a] = -d[a];
+  }
+  const double nl = ((double)normal[3 * p] * l[0] + (double)normal[3 * p + 1] * l[1]) + (double)normal[3 * p + 2] * l[2];
+  const double lam = fmax(0.0, nl);
+  const double w = 0.25 + 0.75 * lam;
+  double alb[3] = {P.albedo[id][0], P.albedo[id][1], P.albedo[id][2]};
+  if (id == albedo_id) {
+    const float a0 = pixel_albedo[3 * p], a1 = pixel_albedo[3 * p + 1], a2 = pixel_albedo[3 * p + 2];
+    if (a0 == a0 && a1 == a1 && a2 == a2) {
+      alb[0] = (double)a0;
+      alb[1] = (double)a1;
+      alb[2] = (double)a2;
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double c = alb[a] * w;
+    double q = floor(255.0 * c + 0.5);
+    q = fmin(fmax(q, 0.0), 255.0);                    // fmax drops a NaN
+    rgb[3 * p + a] = (unsigned char)(int)q;
+  }
+}
+
 static int fill_render_camera(RenderCamera* C, const double* camera, int ortho, int64_t width, int64_t height, double near,
                               double step, int64_t num_steps) {
   MFS_REQUIRE(camera, "null camera");
@@ -796,6 +838,40 @@ int mfs_render_shade3d(const double* camera, int ortho, int64_t width, int64_t h
   const int64_t pixels = (int64_t)C.W * C.H;
   hipLaunchKernelGGL(k_render_shade, dim3((unsigned)((pixels + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0,
                      (hipStream_t)stream, C, P, (const float*)normal, (const int*)shape_id, (unsigned char*)rgb);
+  MFS_LAUNCH_CHECK();
+  return MFS_OK;
+}
+
+int mfs_render_shade_albedo3d(const double* camera, int ortho, int64_t width, int64_t height, const void* normal,
+                              const void* shape_id, int64_t num_colors, const double* albedo_host,
+                              const int* background_host, const double* light_host, const void* pixel_albedo,
+                              int64_t albedo_id, void* rgb, mfs_stream stream) {
+  RenderCamera C;
+  if (int st = fill_render_camera(&C, camera, ortho, width, height, 0.0, 1.0, 1)) return st;
+  MFS_REQUIRE(normal && shape_id && rgb && pixel_albedo, "null normal / shape_id / rgb / pixel_albedo");
+  MFS_REQUIRE(num_colors >= 1 && num_colors <= kMaxVolumes, "1 to 16 colours");
+  MFS_REQUIRE(albedo_id >= 0 && albedo_id < num_colors, "albedo_id must name one of the colours");
+  MFS_REQUIRE(albedo_host && background_host, "null albedo / background");
+  RenderPalette P;
+  memset(&P, 0, sizeof(P));
+  P.n = (int)num_colors;
+  for (int k = 0; k < 3 * P.n; ++k) {
+    MFS_REQUIRE(isfinite(albedo_host[k]), "albedo must be finite");
+    P.albedo[k / 3][k % 3] = albedo_host[k];
+  }
+  for (int k = 0; k < 3; ++k) {
+    MFS_REQUIRE(background_host[k] >= 0 && background_host[k] <= 255, "background must be in 0 .. 255");
+    P.background[k] = background_host[k];
+    if (light_host) {
+      MFS_REQUIRE(isfinite(light_host[k]), "light must be finite");
+      P.light[k] = light_host[k];
+    }
+  }
+  P.has_light = light_host ? 1 : 0;
+  const int64_t pixels = (int64_t)C.W * C.H;
+  hipLaunchKernelGGL(k_render_shade_albedo, dim3((unsigned)((pixels + kRenderBlock - 1) / kRenderBlock)),
+                     dim3(kRenderBlock), 0, (hipStream_t)stream, C, P, (const float*)normal, (const int*)shape_id,
+                     (const float*)pixel_albedo, (int)albedo_id, (unsigned char*)rgb);
   MFS_LAUNCH_CHECK();
   return MFS_OK;
 }

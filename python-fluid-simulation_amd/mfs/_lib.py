@@ -254,6 +254,11 @@ SIGNATURES = {
                                 C.POINTER(_p), C.POINTER(_p), _i, _pd, _pd, _pint, _i, _d, _i64, _i64, _p, _p, _p, _p, _p,
                                 _p]),
     "mfs_render_resolve3d": (_i, [_p, _i64, _i64, _i, _p, _p]),
+    "mfs_attrib_bins3d": (_i64, [_pi64]),
+    "mfs_attrib_keys3d": (_i, [_pi64, _pd, _d, _pd, _p, _i, _i64, _p, _p]),
+    "mfs_attrib_gather3d": (_i, [_pi64, _pd, _d, _i, _d, _p, _i, _p, _i, _i64, _p, _p, _i, _p, _i64, _p, _i64, _p, _p, _p,
+                                 _p]),
+    "mfs_render_shade_albedo3d": (_i, [_pd, _i, _i64, _i64, _p, _p, _i64, _pd, _pint, _pd, _p, _i64, _p, _p]),
 }
 
 _lib = None

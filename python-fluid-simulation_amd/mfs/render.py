@@ -419,9 +419,9 @@ def _palette(colors, count):
     return out
 
 
-def shade(result, camera, colors, background=(255, 255, 255), light=None):
-    """(H, W, 3) uint8 on the result's device: albedo_id * (0.25 + 0.75 * max(0, n . l)), albedo = colour / 255, rounded
-    floor(255 c + 0.5); l = -d, a headlight, or `light`, a vector towards the light; `background` at misses."""
+def hit_points(result, camera):
+    """(H, W, 3) float64 on the result's device: origin + depth * direction of every pixel's ray, NaN at a miss.  The
+    rays follow the camera's rule, operation by operation as tests/render_numpy.py's `rays` restates it."""
     if not isinstance(result, RenderResult):
         raise TypeError(f"result: expected a RenderResult, got {type(result).__name__}")
     if not isinstance(camera, Camera):
@@ -429,7 +429,90 @@ def shade(result, camera, colors, background=(255, 255, 255), light=None):
     H, W = (int(v) for v in result.steps.shape)
     if (camera.width, camera.height) != (W, H):
         raise ValueError(f"camera is {camera.width} x {camera.height}, the result {W} x {H}")
-    albedo = _palette(colors, result.num_shapes)
+    dev, b = result.depth.device, camera.basis()
+    f, r, u, eye = (torch.as_tensor(b[k], dtype=torch.float64, device=dev) for k in ("f", "r", "u", "eye"))
+    i = torch.arange(H, dtype=torch.float64, device=dev).reshape(H, 1, 1)
+    j = torch.arange(W, dtype=torch.float64, device=dev).reshape(1, W, 1)
+    sx = ((j + 0.5) * (2.0 / W) - 1.0) * b["half_w"]
+    sy = (1.0 - (i + 0.5) * (2.0 / H)) * b["half_h"]
+    if b["ortho"]:
+        o, d = (eye + sx * r) + sy * u, f.expand(H, W, 3)
+    else:
+        v = (f + sx * r) + sy * u
+        o, d = eye.expand(H, W, 3), v / torch.sqrt((v[..., 0] ** 2 + v[..., 1] ** 2) + v[..., 2] ** 2).unsqueeze(-1)
+    hit = (result.steps >= 0).unsqueeze(-1)
+    depth = torch.where(hit[..., 0], result.depth, 0.0).unsqueeze(-1)
+    return torch.where(hit, o + depth * d, math.nan)
+
+
+class Colormap:
+    """Piecewise linear colours over stops (t, (r, g, b)), t ascending from 0 to 1, colours in 0 .. 255; or the name of a
+    preset.  nan_color: the (r, g, b) a NaN value gets; None: a NaN value gives a NaN albedo, which the shading kernel
+    answers with the palette's colour."""
+
+    PRESETS = {
+        "speed": [(0.0, (40, 120, 230)), (1.0, (255, 255, 255))],                     # the liquid's colour to white
+        "heat": [(0.0, (0, 0, 0)), (0.4, (200, 30, 0)), (0.8, (255, 200, 0)), (1.0, (255, 255, 255))],
+        "diverging": [(0.0, (40, 70, 200)), (0.5, (245, 245, 245)), (1.0, (200, 40, 40))],
+    }
+
+    def __init__(self, stops, nan_color=None):
+        if isinstance(stops, str):
+            if stops not in self.PRESETS:
+                raise ValueError(f"colormap: expected one of {sorted(self.PRESETS)} or a list of stops, got {stops!r}")
+            stops = self.PRESETS[stops]
+        try:
+            self.t = [float(s[0]) for s in stops]
+            self.colors = [tuple(T.as_f64_list(s[1], 3)) for s in stops]
+        except (TypeError, ValueError, IndexError):
+            raise ValueError("colormap: expected stops (t, (r, g, b))") from None
+        if len(self.t) < 2 or self.t[0] != 0.0 or self.t[-1] != 1.0 or any(b <= a for a, b in zip(self.t, self.t[1:])):
+            raise ValueError(f"colormap: stops must ascend strictly from t = 0 to t = 1, got {self.t}")
+        if not all(0.0 <= v <= 255.0 for c in self.colors for v in c):
+            raise ValueError("colormap: colour components must be in 0 .. 255")
+        self.nan_color = None if nan_color is None else tuple(T.as_f64_list(nan_color, 3))
+        if self.nan_color is not None and not all(0.0 <= v <= 255.0 for v in self.nan_color):
+            raise ValueError("colormap: nan_color components must be in 0 .. 255")
+
+    def slope(self):
+        """the largest |d albedo / d t| over the segments and channels"""
+        return max(abs(b - a) / 255.0 / (tb - ta) for ta, tb, ca, cb in zip(self.t, self.t[1:], self.colors, self.colors[1:])
+                   for a, b in zip(ca, cb))
+
+    def apply(self, values, lo, hi):
+        """float32 albedo in [0, 1], shape values.shape + (3,), on the values' device: t = clamp((v - lo) / (hi - lo), 0, 1)
+        in float32, then in segment k (t_k <= t, the last one at t = 1) c = c_k + (c_{k+1} - c_k) * ((t - t_k) / (t_{k+1} -
+        t_k)) with c = colour / 255 rounded to float32.  A NaN value gives NaN, or nan_color."""
+        lo, hi = float(lo), float(hi)
+        if not (math.isfinite(lo) and math.isfinite(hi) and hi > lo):
+            raise ValueError(f"colour range: expected finite lo < hi, got ({lo}, {hi})")
+        if not isinstance(values, torch.Tensor):
+            raise TypeError(f"values: expected a torch tensor, got {type(values).__name__}")
+        v = values.to(torch.float32)
+        f32 = lambda a: torch.tensor(a, dtype=torch.float64).to(torch.float32).to(v.device)  # noqa: E731
+        t = torch.clamp((v - f32(lo)) / (f32(hi) - f32(lo)), 0.0, 1.0)
+        ts, cs = f32(self.t), f32(self.colors) / 255.0
+        k = torch.clamp(torch.bucketize(t, ts, right=True) - 1, 0, len(self.t) - 2)      # a NaN lands in the last segment
+        s = ((t - ts[k]) / (ts[k + 1] - ts[k])).unsqueeze(-1)
+        c = cs[k] + (cs[k + 1] - cs[k]) * s
+        if self.nan_color is not None:
+            c = torch.where(torch.isnan(v).unsqueeze(-1), f32(self.nan_color) / 255.0, c)
+        return c
+
+
+def shade(result, camera, colors, background=(255, 255, 255), light=None, albedo=None, albedo_id=0):
+    """(H, W, 3) uint8 on the result's device: albedo_id * (0.25 + 0.75 * max(0, n . l)), albedo = colour / 255, rounded
+    floor(255 c + 0.5); l = -d, a headlight, or `light`, a vector towards the light; `background` at misses.
+    albedo: None, or (H, W, 3) float32 in 0 .. 1 on the result's device: the pixels of shape `albedo_id` take it in
+    place of that shape's colour, except where it is NaN."""
+    if not isinstance(result, RenderResult):
+        raise TypeError(f"result: expected a RenderResult, got {type(result).__name__}")
+    if not isinstance(camera, Camera):
+        raise TypeError(f"camera: expected an mfs.render.Camera, got {type(camera).__name__}")
+    H, W = (int(v) for v in result.steps.shape)
+    if (camera.width, camera.height) != (W, H):
+        raise ValueError(f"camera is {camera.width} x {camera.height}, the result {W} x {H}")
+    palette = _palette(colors, result.num_shapes)
     bg = [int(v) for v in background]
     if len(bg) != 3 or not all(0 <= v <= 255 for v in bg):
         raise ValueError(f"background: expected (r, g, b) in 0 .. 255, got {tuple(background)}")
@@ -438,14 +521,34 @@ def shade(result, camera, colors, background=(255, 255, 255), light=None):
         if not (np.isfinite(light).all() and float(np.abs(light).max()) > 0):
             raise ValueError("light: expected a finite, non-zero vector towards the light")
         light = _unit(light)
+    if albedo is not None:
+        if not isinstance(albedo, torch.Tensor):
+            raise TypeError(f"albedo: expected a torch tensor on the GPU, got {type(albedo).__name__}")
+        if tuple(albedo.shape) != (H, W, 3) or albedo.dtype != torch.float32 or not albedo.is_contiguous():
+            raise ValueError(f"albedo: expected a C-contiguous ({H}, {W}, 3) float32 tensor, got {tuple(albedo.shape)} "
+                             f"{albedo.dtype}")
+        if not (0 <= int(albedo_id) < result.num_shapes):
+            raise ValueError(f"albedo_id {albedo_id}: the result has shapes 0 .. {result.num_shapes - 1}")
     if not result.normal.is_cuda:
         raise TypeError(f"result is on {result.normal.device}; shading runs on the GPU only (no CPU fallback)")
     lib = _lib.load()
     dev = result.normal.device
+    if albedo is not None:
+        if albedo.device != dev:
+            raise TypeError(f"albedo is on {albedo.device}, the result on {dev}")
+        with torch.cuda.device(dev):
+            rgb = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+            _lib.check(lib.mfs_render_shade_albedo3d(_lib.f64x(camera.packed()), int(camera.ortho), W, H,
+                                                     T.ptr(result.normal), T.ptr(result.shape_id), len(palette) // 3,
+                                                     _lib.f64x(palette), (ctypes.c_int * 3)(*bg),
+                                                     None if light is None else _lib.f64x(light), T.ptr(albedo),
+                                                     int(albedo_id), T.ptr(rgb), T.stream()),
+                       "mfs_render_shade_albedo3d")
+        return rgb
     with torch.cuda.device(dev):
         rgb = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
         _lib.check(lib.mfs_render_shade3d(_lib.f64x(camera.packed()), int(camera.ortho), W, H, T.ptr(result.normal),
-                                          T.ptr(result.shape_id), len(albedo) // 3, _lib.f64x(albedo), (ctypes.c_int * 3)(*bg),
+                                          T.ptr(result.shape_id), len(palette) // 3, _lib.f64x(palette), (ctypes.c_int * 3)(*bg),
                                           None if light is None else _lib.f64x(light), T.ptr(rgb), T.stream()),
                    "mfs_render_shade3d")
     return rgb
@@ -532,3 +635,67 @@ def simulation_paths(sim, camera, what, look, step=None, trace=False):
     if trace:
         return Scene(shapes).trace(camera, look, step), look
     return image_paths(shapes, camera, look, step)
+
+
+def simulation_box(sim):
+    """the simulation's bounds as a gather's box: float64(BOUND_MIN) .. + float64(BOUND_SIZE)"""
+    lo = np.asarray(sim.BOUND_MIN, np.float64)
+    return tuple(float(v) for v in lo), tuple(float(v) for v in lo + np.asarray(sim.BOUND_SIZE, np.float64))
+
+
+def simulation_values(sim, values):
+    """`values` of `sample_particles` / `color_by` as a tensor: "speed" = |particle.v|, "velocity" = particle.v"""
+    if isinstance(values, str):
+        if values == "speed":
+            return torch.linalg.vector_norm(sim.particle.v, dim=1)
+        if values == "velocity":
+            return sim.particle.v
+        raise ValueError(f'values: expected "velocity", "speed" or a tensor, got {values!r}')
+    return values
+
+
+def simulation_colored(sim, camera, what, colors, step, color_by, color_range, colormap):
+    """the image of `NotebookSimulation.render(color_by=...)`: the liquid's pixels take the particles' data, gathered at
+    their hit points with the rendered skin's influence over the simulation's bounds, as their albedo"""
+    from . import attrib as _attrib
+    names = (what,) if isinstance(what, str) else tuple(what)
+    if "liquid" not in names:
+        raise ValueError(f'color_by colours the liquid: "liquid" must be in what, got {what!r}')
+    if isinstance(color_by, str) and color_by != "speed":
+        raise ValueError(f'color_by: expected "speed", a (P,) or a (P, 3) tensor, got {color_by!r}')
+    cmap = colormap if isinstance(colormap, Colormap) else Colormap(colormap)
+    if color_range is not None:
+        lo, hi = (float(v) for v in color_range)
+        if not (math.isfinite(lo) and math.isfinite(hi) and hi > lo):
+            raise ValueError(f"color_range: expected finite (lo, hi), lo < hi, got {tuple(color_range)}")
+    n = int(sim.particle.x.shape[0])
+    data = simulation_values(sim, color_by)
+    if not isinstance(data, torch.Tensor) or tuple(data.shape) not in ((n,), (n, 3)):
+        raise ValueError(f'color_by: expected "speed", a ({n},) or a ({n}, 3) tensor, got '
+                         f"{tuple(data.shape) if isinstance(data, torch.Tensor) else type(data).__name__}")
+    names, shapes = simulation_shapes(sim, what)
+    if colors is None:
+        colors = [LIQUID_COLOR if w == "liquid" else SOLID_COLOR for w in names]
+    _palette(colors, len(shapes))
+    liquid = names.index("liquid")
+    result = Scene(shapes).render(camera, step)
+    H, W = camera.height, camera.width
+    points = torch.where((result.shape_id == liquid).unsqueeze(-1), hit_points(result, camera), math.nan)
+    got, _ = _attrib.gather(points.reshape(-1, 3), sim.particle.x, data, shapes[liquid].influence, simulation_box(sim))
+    if data.dim() == 2:
+        albedo = torch.clamp(got, 0.0, 1.0).reshape(H, W, 3)              # a dye: the albedo itself (clamp keeps a NaN)
+    else:
+        if color_range is None:
+            lo, hi = 0.0, float(data.max().item()) if n else 0.0
+            if not (math.isfinite(hi) and hi > lo):
+                hi = 1.0
+        albedo = cmap.apply(got.reshape(H, W), lo, hi)
+    return shade(result, camera, colors, albedo=albedo.contiguous(), albedo_id=liquid)
+
+
+def simulation_sample(sim, points, values="velocity"):
+    """`NotebookSimulation.sample_particles`: (values (Q, C), weight (Q,)) of the particles' data at `points`, gathered
+    with the skin's default influence over the simulation's bounds"""
+    from . import attrib as _attrib, skin as _skin
+    influence = 3.0 * _skin.default_radius(0.5 * sim.GDX)
+    return _attrib.gather(points, sim.particle.x, simulation_values(sim, values), influence, simulation_box(sim))

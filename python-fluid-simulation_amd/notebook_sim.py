@@ -172,16 +172,31 @@ class NotebookSimulation:
         `solid_levelset.phi` (the analytic and the mesh bodies united); shape ids count in the order of `what`."""
         return _render.simulation_result(self, camera, what, step)
 
-    def render(self, camera, what=("liquid", "solid"), colors=None, step=None, look=None):
+    def render(self, camera, what=("liquid", "solid"), colors=None, step=None, look=None, color_by=None, color_range=None,
+               colormap="speed"):
         """`render_result` shaded: an (H, W, 3) uint8 image on the GPU, white where a ray meets nothing;
         `mfs.render.save_png` writes it.  colors: one (r, g, b) in 0 .. 255 per entry of `what`.
         look: None: headlight Lambert on opaque surfaces, as above.  An `mfs.render.Look` with one material per entry of
         `what` (the skin takes the liquid one), or "water" (`mfs.render.Look.water`: the skin refracts at ior 1.33 and
         absorbs, the solids are opaque and cast shadows, a light from above, 2 x 2 rays per pixel): the paths of
-        `mfs.render.Scene.trace`, resolved; `colors` then plays no part."""
+        `mfs.render.Scene.trace`, resolved; `colors` then plays no part.
+        color_by: None, or what colours the liquid's pixels (`mfs.attrib.gather` at their hit points, with the skin's
+        influence, over the simulation's bounds): "speed" = |particle.v| or a (P,) tensor, through `colormap` (an
+        `mfs.render.Colormap` or a preset's name) over `color_range` = (lo, hi), None: (0, the largest value); or a
+        (P, 3) tensor, a dye: the albedo itself, held in 0 .. 1.  Not with `look`: the paths are not coloured."""
+        if color_by is not None:
+            if look is not None:
+                raise ValueError("color_by and look do not combine: the paths of look are not coloured by particle data")
+            return _render.simulation_colored(self, camera, what, colors, step, color_by, color_range, colormap)
         if look is None:
             return _render.simulation_image(self, camera, what, colors, step)
         return _render.simulation_paths(self, camera, what, look, step)
+
+    def sample_particles(self, points, values="velocity"):
+        """What the particles carry at `points` (Q, 3), for probes and mesh vertices: (values (Q, C) float32, weight (Q,))
+        of `mfs.attrib.gather` with the skin's influence over the simulation's bounds; NaN where no particle is within
+        reach.  values: "velocity" = particle.v, "speed" = |particle.v|, or a (P,) / (P, C) tensor, C <= 4."""
+        return _render.simulation_sample(self, points, values)
 
     def step(self, duration_left=float("inf"), timings=None):
         """One pass of the loop body (ipynb:4571-4667, solver == 'apic').  Returns the dt it took."""
@@ -309,8 +324,13 @@ class SlabNotebookSimulation(NotebookSimulation):
         raise NotImplementedError("render() is single-GPU: gather the particles and the level set to one rank and call "
                                   "mfs.render.image")
 
-    def render(self, camera, what=("liquid", "solid"), colors=None, step=None, look=None):
+    def render(self, camera, what=("liquid", "solid"), colors=None, step=None, look=None, color_by=None, color_range=None,
+               colormap="speed"):
         return self.render_result(camera, what, step)
+
+    def sample_particles(self, points, values="velocity"):
+        raise NotImplementedError("sample_particles() is single-GPU: gather the particles to one rank and call "
+                                  "mfs.attrib.gather")
 
     def close(self):
         self.PressureSolver.close()

@@ -98,6 +98,12 @@ class NotebookSimulation2D:
     def skin(self, *args, **kw):
         raise NotImplementedError("skin() is 3D (NotebookSimulation.skin, mfs.skin): the 2D class has `surface()`")
 
+    def render(self, *args, **kw):
+        raise NotImplementedError("render() is 3D (NotebookSimulation.render, mfs.render), color_by included")
+
+    def sample_particles(self, *args, **kw):
+        raise NotImplementedError("sample_particles() is 3D (NotebookSimulation.sample_particles, mfs.attrib)")
+
     def step(self, duration_left=float("inf"), timings=None):
         """One pass of the loop body.  Returns the dt it took."""
         p, g, sl, fl, fv = self.particle, self.grid, self.solid_levelset, self.fluid_levelset, self.fluid_volume
