@@ -1061,8 +1061,32 @@ def nb_fluid_volume(bound_min, cell_size, gres, px, pvol, gvol, stats=None):
 # rigid-body signed distances -- solver/sdf3D.py
 # rb: one (10,4) float64 block; see generate_rb :277-305.  Scalar per-point restatements (test sizes only).
 # =============================================================================
-def _sdf_to_body(rb, pos):
-    """inv_rigid (:31-40) then matvecmul4 (:19-29), in their accumulation order."""
+def _tr(trace, name, cond, gap=None):
+    """`cond`, after counting it under (name, outcome) in the dict `trace` (if one is given).  `gap`, the difference of the
+    two compared quantities, goes into trace["margin"] (the least |gap| seen) and trace["gaps"][name] (the least per name)."""
+    cond = bool(cond)
+    if trace is not None:
+        trace[(name, cond)] = trace.get((name, cond), 0) + 1
+        if gap is not None and gap == gap:
+            g = abs(float(gap))
+            trace["margin"] = min(trace.get("margin", np.inf), g)
+            gaps = trace.setdefault("gaps", {})
+            gaps[name] = min(gaps.get(name, np.inf), g)
+    return cond
+
+
+def _mg(mag, *vals):
+    """mag["M"] = the largest finite magnitude among itself and `vals` (if a dict is given)"""
+    if mag is not None:
+        for v in vals:
+            v = abs(float(v))
+            if np.isfinite(v) and v > mag.get("M", 0.0):
+                mag["M"] = v
+
+
+def _sdf_to_body(rb, pos, mag=None):
+    """inv_rigid (:31-40) then matvecmul4 (:19-29), in their accumulation order.  `mag`, if a dict, takes under "M" the
+    largest sum of the magnitudes of one row's terms (every partial sum of that row is at most that)."""
     T, Rm = rb[1:5], rb[5:9]
     out = np.zeros(3)
     for i in range(3):
@@ -1074,10 +1098,11 @@ def _sdf_to_body(rb, pos):
             tmp += Rm[j, i] * pos[j]
         tmp += t3
         out[i] = tmp
+        _mg(mag, sum(abs(Rm[j, i] * T[j, 3]) + abs(Rm[j, i] * pos[j]) for j in range(3)))
     return out
 
 
-def _sdf_to_world(rb, prb):
+def _sdf_to_world(rb, prb, mag=None):
     """mat_TR (:12-17) then matvecmul4."""
     T, Rm = rb[1:5], rb[5:9]
     out = np.zeros(3)
@@ -1087,59 +1112,101 @@ def _sdf_to_world(rb, prb):
             tmp += Rm[i, j] * prb[j]
         tmp += T[i, 3]
         out[i] = tmp
+        _mg(mag, sum(abs(Rm[i, j] * prb[j]) for j in range(3)) + abs(T[i, 3]))
     return out
 
 
-def _sdf_eval_one(rb, pos):
+def _sdf_eval_one(rb, pos, trace=None, mag=None):
+    """one body's signed distance.  `trace`, if a dict, counts each side of every comparison (`_tr`); `mag`, if a dict, takes
+    under "M" the largest intermediate magnitude (a length: sums of |term| for the frame changes, the parameters, the
+    distances).  Neither changes the result."""
     kind, flipped = int(rb[0, 0] // 2), bool(rb[0, 0] % 2)
     if kind == 0:                                            # sphere_eval :53-66
         d = pos - np.array([rb[1, 3], rb[2, 3], rb[3, 3]])
         sd = (d[0] ** 2 + d[1] ** 2 + d[2] ** 2) ** 0.5 - rb[0, 1]
+        _mg(mag, *pos, rb[1, 3], rb[2, 3], rb[3, 3], rb[0, 1], sd + rb[0, 1])
     elif kind == 1:                                          # box_eval :86-108
-        prb = _sdf_to_body(rb, pos)
+        prb = _sdf_to_body(rb, pos, mag)
         tmp, mx = 0.0, -100
         for i in range(3):
             disp = abs(prb[i]) - rb[0, 1 + i] / 2
-            if disp > 0:
+            if _tr(trace, "box_eval disp > 0", disp > 0, disp):
                 tmp += disp ** 2
-            if mx < disp:
+            if _tr(trace, "box_eval max_disp < disp", mx < disp, mx - disp):
                 mx = disp
+            _mg(mag, rb[0, 1 + i] / 2)
         sd = tmp ** 0.5
-        if mx < 0:
+        _mg(mag, sd, mx)
+        if _tr(trace, "box_eval max_disp < 0", mx < 0, mx):
             sd += mx
     else:                                                    # cylinder_eval :148-172 (y_clip: see csrc/mfs_sdf.hip header)
-        prb = _sdf_to_body(rb, pos)
+        prb = _sdf_to_body(rb, pos, mag)
         hh = rb[0, 2] / 2
-        y_clip = -hh if prb[1] < -hh else (hh if prb[1] > hh else prb[1])
+        if _tr(trace, "cylinder_eval y < -hh", prb[1] < -hh, prb[1] + hh):
+            y_clip = -hh
+        elif _tr(trace, "cylinder_eval y > hh", prb[1] > hh, prb[1] - hh):
+            y_clip = hh
+        else:
+            y_clip = prb[1]
         sd = (prb[0] ** 2 + prb[2] ** 2) ** 0.5 - rb[0, 1]
-        cap = y_clip == hh or y_clip == -hh
-        if sd < 0:
-            sd = abs(y_clip - prb[1]) if cap else max(sd, prb[1] - hh, -(prb[1] + hh))
+        _mg(mag, hh, rb[0, 1], sd + rb[0, 1], y_clip - prb[1])
+        cap = _tr(trace, "cylinder_eval y_clip == hh", y_clip == hh) or _tr(trace, "cylinder_eval y_clip == -hh", y_clip == -hh)
+        if _tr(trace, "cylinder_eval sd < 0", sd < 0, sd):
+            if cap:
+                sd = abs(y_clip - prb[1])
+            else:
+                c3 = sorted((sd, prb[1] - hh, -(prb[1] + hh)))
+                _tr(trace, "cylinder_eval max is radial", c3[2] == sd, c3[2] - c3[1])
+                sd = max(sd, prb[1] - hh, -(prb[1] + hh))
         elif cap:
             sd = (sd ** 2 + abs(y_clip - prb[1]) ** 2) ** 0.5
+        _tr(trace, "cylinder_eval cap", cap)
+        _mg(mag, sd)
     return -sd if flipped else sd
 
 
-def sdf_evaluate(rb_d, sd, vel, position):
-    """evaluate :260-270 -> evaluate_kernel :218-239."""
+def sdf_evaluate(rb_d, sd, vel, position, trace=None, mag=None):
+    """evaluate :260-270 -> evaluate_kernel :218-239.  Rows of a type code beyond the cylinder's (the mesh code 6) leave the
+    minimum alone, as csrc/mfs_sdf.hip does.  `trace`: a dict of comparison counters (`_tr`); with it, trace["point_margin"]
+    lists the least gap of each point.  `mag`, if a dict, receives under "sd" the largest intermediate magnitude per point."""
     vel *= 0
     P = position.reshape(-1, 3)
     S, V = sd.reshape(-1), vel.reshape(-1, 3)
+    if mag is not None:
+        mag["sd"] = np.zeros(P.shape[0])
     for p in range(P.shape[0]):
         min_sd, idx = 100, 0
+        m1 = None if mag is None else {}
+        if trace is not None:
+            trace["margin"] = np.inf
         for i in range(rb_d.shape[0]):
-            d = _sdf_eval_one(rb_d[i], P[p].astype(F64))
-            if d < min_sd:
+            if int(rb_d[i, 0, 0] // 2) > 2:
+                continue
+            d = _sdf_eval_one(rb_d[i], P[p].astype(F64), trace, m1)
+            if _tr(trace, "evaluate d < min_sd", d < min_sd, d - min_sd):
                 min_sd, idx = d, i
         S[p] = min_sd
-        if min_sd <= 0:
+        if _tr(trace, "evaluate min_sd <= 0", min_sd <= 0, min_sd):
             V[p, :] = rb_d[idx, -1, :3]
+        if trace is not None:
+            trace.setdefault("point_margin", []).append(trace["margin"])
+        if mag is not None:
+            mag["sd"][p] = m1.get("M", 0.0)
 
 
-def sdf_project(rb_d, position):
-    """project :272-278 -> project_kernel :241-258 (in place; every body in turn)."""
+def sdf_project(rb_d, position, trace=None, mag=None, round_each=True):
+    """project :272-278 -> project_kernel :241-258 (in place; every body in turn).  Unknown type codes are skipped, as in
+    sdf_evaluate.  `trace` as there.  `mag`, if a dict, receives under "position" per point the largest intermediate magnitude
+    of the chain times the gain r / dist (where above 1) of every radial projection the point went through: what a
+    perturbation of an earlier body's result can have grown to.  round_each=False (not the reference's behaviour; for tests
+    of the tests) rounds a float32 position once at the end instead of after every body."""
+    if mag is not None:
+        mag["position"] = np.zeros(position.shape[0])
     for p in range(position.shape[0]):
         pos = position[p].astype(F64)
+        m1, gain = (None if mag is None else {}), 1.0
+        if trace is not None:
+            trace["margin"] = np.inf
         for i in range(rb_d.shape[0]):
             rb = rb_d[i]
             kind, flipped = int(rb[0, 0] // 2), bool(rb[0, 0] % 2)
@@ -1148,48 +1215,74 @@ def sdf_project(rb_d, position):
                 d = pos - c
                 dist = (d[0] ** 2 + d[1] ** 2 + d[2] ** 2) ** 0.5
                 sd = dist - rb[0, 1]
+                _mg(m1, *pos, *c, dist, rb[0, 1])
                 if flipped:
                     sd = -sd
-                if sd < 0:
+                if _tr(trace, "sphere_project sd < 0", sd < 0, sd):
                     pos = d / dist * rb[0, 1] + c
+                    gain *= max(1.0, rb[0, 1] / dist) if dist > 0 else 1.0
             elif kind == 1:                                  # box_project :110-146
-                prb = _sdf_to_body(rb, pos)
+                prb = _sdf_to_body(rb, pos, m1)
                 h = rb[0, 1:4] / 2
-                in_out = int(np.sum((prb > h) | (prb < -h)))
+                _mg(m1, *h)
+                in_out = 0
+                for k in range(3):
+                    if (_tr(trace, "box_project prb > h", prb[k] > h[k], prb[k] - h[k])
+                            or _tr(trace, "box_project prb < -h", prb[k] < -h[k], prb[k] + h[k])):
+                        in_out += 1
                 if flipped:                                  # `% 2 and ~(in_out)`: ~ is bitwise, always true (:126)
-                    pos = _sdf_to_world(rb, np.clip(prb, -h, h))
-                elif in_out == 0:
+                    pos = _sdf_to_world(rb, np.clip(prb, -h, h), m1)
+                elif _tr(trace, "box_project in_out == 0", in_out == 0):
                     index, dist_xyz = 0, 100
                     for k in range(3):
-                        if h[k] - prb[k] < dist_xyz:
+                        if _tr(trace, "box_project h - prb < dist", h[k] - prb[k] < dist_xyz, h[k] - prb[k] - dist_xyz):
                             dist_xyz, index = h[k] - prb[k], k * 2
-                        if prb[k] + h[k] < dist_xyz:
+                        if _tr(trace, "box_project prb + h < dist", prb[k] + h[k] < dist_xyz, prb[k] + h[k] - dist_xyz):
                             dist_xyz, index = prb[k] + h[k], k * 2 + 1
                     prb[index // 2] += dist_xyz * (-1) ** (index % 2)
-                    pos = _sdf_to_world(rb, prb)
-            else:                                            # cylinder_project :174-216
-                prb = _sdf_to_body(rb, pos)
+                    pos = _sdf_to_world(rb, prb, m1)
+            elif kind == 2:                                  # cylinder_project :174-216
+                prb = _sdf_to_body(rb, pos, m1)
                 hh = rb[0, 2] / 2
-                y_clip = -hh if prb[1] < -hh else (hh if prb[1] > hh else prb[1])
+                if _tr(trace, "cylinder_project y < -hh", prb[1] < -hh, prb[1] + hh):
+                    y_clip = -hh
+                elif _tr(trace, "cylinder_project y > hh", prb[1] > hh, prb[1] - hh):
+                    y_clip = hh
+                else:
+                    y_clip = prb[1]
                 dist = (prb[0] ** 2 + prb[2] ** 2) ** 0.5
                 sd = dist - rb[0, 1]
+                _mg(m1, hh, dist, rb[0, 1])
+                radial = False
                 if flipped:
-                    if abs(y_clip) == hh or sd > 0:
-                        if sd >= 0:
+                    if (_tr(trace, "cylinder_project flipped |y_clip| == hh", abs(y_clip) == hh)
+                            or _tr(trace, "cylinder_project flipped sd > 0", sd > 0, sd)):
+                        if _tr(trace, "cylinder_project flipped sd >= 0", sd >= 0, sd):
                             prb[0], prb[2] = prb[0] / dist * rb[0, 1], prb[2] / dist * rb[0, 1]
+                            radial = True
                         prb[1] = y_clip
-                    pos = _sdf_to_world(rb, prb)
-                elif sd < 0 and abs(y_clip) != hh:
+                    pos = _sdf_to_world(rb, prb, m1)
+                elif (_tr(trace, "cylinder_project sd < 0", sd < 0, sd)
+                      and _tr(trace, "cylinder_project |y_clip| != hh", abs(y_clip) != hh)):
                     mv = max(sd, prb[1] - hh, -(prb[1] + hh))
-                    if mv == sd:
+                    c3 = sorted((sd, prb[1] - hh, -(prb[1] + hh)))
+                    if _tr(trace, "cylinder_project mv == sd", mv == sd, c3[2] - c3[1]):
                         prb[0], prb[2] = prb[0] / dist * rb[0, 1], prb[2] / dist * rb[0, 1]
-                    elif mv == prb[1] - hh:
+                        radial = True
+                    elif _tr(trace, "cylinder_project mv == y - hh", mv == prb[1] - hh):
                         prb[1] = hh
                     else:
                         prb[1] = -hh
-                    pos = _sdf_to_world(rb, prb)
-            pos = pos.astype(position.dtype).astype(F64)     # the reference writes into the array row
+                    pos = _sdf_to_world(rb, prb, m1)
+                if radial and dist > 0:
+                    gain *= max(1.0, rb[0, 1] / dist)
+            if round_each:
+                pos = pos.astype(position.dtype).astype(F64)     # the reference writes into the array row
         position[p] = pos
+        if trace is not None:
+            trace.setdefault("point_margin", []).append(trace["margin"])
+        if mag is not None:
+            mag["position"][p] = m1.get("M", 0.0) * gain
 
 
 # =============================================================================
